@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CG iterations/s and matVec HBM GB/s on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 65536] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 65536] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -30,11 +30,23 @@ s8(d)) / the average matVec kernel duration measured with HIP events on the
 stream the kernel runs on, over the timed region.  `roofline.traffic` is the
 HBM bytes per launch from rocprofv3 PMC counters (profiles/pmc_summary.json,
 FETCH_SIZE doubled per the gfx950 correction) when a summary for this
-workload exists, else null.  `cpu_baseline` times the oracle's fp32-ref
-restatement of serialConjugate.c (bit-identical to it, tests/test_oracle.py)
-on one host core, on a bounded sample: 5 iterations of the same system (~10 s);
+workload exists, else null.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step left a caller of
+cgx_iterate: DIR/x.npy (the iterate, float64; a fixed seeded sample when it
+is larger than 32 MB) and DIR/rr.npy (the recurrence's r.r); the system and
+x0 are the same bits in every run with the same arguments.
+
+--full adds the legs that take runs of their own, on the host after the
+timed region: `cpu_baseline` times the oracle's fp32-ref restatement of
+serialConjugate.c (bit-identical to it, tests/test_oracle.py) on one host
+core, on a bounded sample: 5 iterations of the same system (~10 s);
+`cpu_baseline_mt` the fp64 oracle on 16 host threads;
 `cpu_baseline_reference` runs serialConjugate.c itself (oracle/_ref, built
-from the reference's sources) at its compiled N=8192 in the same run.
+from the reference's sources) at its compiled N=8192 in the same run; the
+Poisson workload gets its CPU baseline and the comparison of x with the
+oracle.  --no-cpu leaves them out of a --full run.
 """
 from __future__ import annotations
 
@@ -324,6 +336,26 @@ def poisson_oracle_check(m: int, iters: int, x_gpu) -> dict:
     return {"oracle_iterations": iters, "x_vs_oracle": rel, "x_vs_oracle_tol": 1e-9, "oracle_agrees": rel <= 1e-9}
 
 
+DUMP_MAX_ELEMS = 4 << 20  # 32 MB of float64 per array, under the 64 MB a dump may take in all
+
+
+def dump_outputs(dirpath: str, x, rr: float) -> dict:
+    """--dump-outputs: what the timed path left its caller after the last timed
+    step, as float64 .npy files: x (the iterate cgx_get_x returns) and rr (the
+    recurrence's r.r, cgx_stats.rr).  An x of more than DUMP_MAX_ELEMS
+    elements is sampled at indices drawn once from SEED (sorted, the same for
+    every run of the same size).  Returns what was written, for the line."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    x = np.asarray(x, np.float64)
+    sampled = x.size > DUMP_MAX_ELEMS
+    if sampled:
+        x = x[np.sort(np.random.default_rng(SEED).integers(0, x.size, DUMP_MAX_ELEMS))]
+    np.save(os.path.join(dirpath, "x.npy"), x)
+    np.save(os.path.join(dirpath, "rr.npy"), np.array([rr], np.float64))
+    return {"dir": dirpath, "x": {"elements": int(x.size), "sampled": sampled}, "rr": {"elements": 1}}
+
+
 # The phases that tile an iteration on the compute stream (cgx.h CGX_PH_*):
 # their medians add up to about the iteration time.
 TILING_PHASES = ("matvec_own", "gather_exposed", "matvec", "combine_pap", "update_r", "combine_rr", "update_xp", "gap")
@@ -437,7 +469,14 @@ def main(argv=None) -> int:
     ap.add_argument("--devices", default=None,
                     help="without a launcher: the devices of the row blocks, comma-separated (default 0..N-1 for "
                          "--gpus N); repeats put several row blocks on one GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs that take runs of their own: the CPU "
+                         "baselines (oracle port on 1 and 16 host cores, serialConjugate.c itself) and, for "
+                         "--workload poisson, the comparison of x with the oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU legs (a plain run has none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/x.npy (the iterate after the last timed step, float64; "
+                         "a fixed seeded sample when larger than 32 MB) and DIR/rr.npy (the recurrence's r.r)")
     ap.add_argument("--cpu-n", type=int, default=None, help="N for the CPU baseline (default: --n)")
     args = ap.parse_args(argv)
 
@@ -555,7 +594,9 @@ def main(argv=None) -> int:
     # residual is above rounding (x and r updated consistently at full size)
     rr_rec = st.rr
     rnorm, bnorm = solver.residual_norm()
-    x_gpu = solver.get_x() if (poisson and world == 1 and not args.no_cpu and rank == 0) else None
+    cpu_legs = args.full and not args.no_cpu
+    # x after the last timed step (in rank mode cgx_get_x is an allgather: every rank calls it)
+    x_gpu = solver.get_x() if (args.dump_outputs or (poisson and world == 1 and cpu_legs and rank == 0)) else None
     solver.close()
 
     if rank != 0:
@@ -686,11 +727,13 @@ def main(argv=None) -> int:
     if devices:
         out["config"]["row_blocks"] = len(devices)
         out["multi_device"] = local_summary(devices, peer_flag, ctx_flags)
-    if world == 1 and not args.no_cpu and poisson:
+    if args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, x_gpu, rr_rec)
+    if world == 1 and cpu_legs and poisson:
         out["cpu_baseline"] = cpu_baseline_poisson(m)
         out["check"].update(poisson_oracle_check(m, args.warmup + args.steps, x_gpu))
         del x_gpu
-    elif world == 1 and not args.no_cpu and not stream and not symmetric:
+    elif world == 1 and cpu_legs and not stream and not symmetric:
         out["cpu_baseline"] = cpu_baseline(args.cpu_n or n)
         out["cpu_baseline_mt"] = cpu_baseline_mt(args.cpu_n or n)
         ref = cpu_baseline_reference(n_bench=n)

@@ -378,3 +378,31 @@ def test_bench_single_gpu_line():
     # (a host stall before the first sampled iteration lands in ms_per_step alone)
     assert abs(ph["tiling_mean_sum_over_ms_per_step"] - 1) <= 0.10, ph
     assert out["check"]["relres"] < 1e-10
+
+
+@pytest.mark.timeout(200)
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) has no CPU leg in its line, --steps sets the
+    timed steps, and --dump-outputs leaves what the last timed step computed:
+    x after warmup + steps iterations from x0 = 0 on the seeded system, equal
+    to the fp64 oracle's after as many (1e-10, this file's pin), and the
+    recurrence's r.r the line's check block was made from."""
+    n, steps, warmup = 2048, 3, 1
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1", "--size", str(n),
+           "--steps", str(steps), "--warmup", str(warmup), "--settle", "0", "--dump-outputs", str(d)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=150)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert not [k for k in out if k.startswith("cpu_baseline")], sorted(out)
+    assert out["steps"] == steps and out["ms_per_step"] == pytest.approx(1e3 / out["value"])
+    assert sorted(f.name for f in d.iterdir()) == ["rr.npy", "x.npy"]
+    x = np.load(d / "x.npy", allow_pickle=False)
+    rr = np.load(d / "rr.npy", allow_pickle=False)
+    assert x.dtype == np.float64 and x.shape == (n,) and rr.dtype == np.float64 and rr.shape == (1,)
+    A, b = oracle.spd_hash(n, seed=42, dtype=np.float64)
+    xo, _ = oracle.cg_f64(A, b, np.zeros(n), max_iter=warmup + steps, eps=-1.0)
+    assert rel(x, xo) <= TOL
+    assert np.sqrt(rr[0]) / np.linalg.norm(b) == pytest.approx(out["check"]["recurrence_relres"], rel=1e-9)

@@ -81,6 +81,30 @@ def test_check_summary():
     assert "recurrence_agrees" not in c and c["relres"] == 1e-15
 
 
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: x and rr as float64 .npy; an x above the cap is sampled
+    at the same seeded indices every time."""
+    import numpy as np
+
+    import bench
+    x = np.arange(1000, dtype=np.float64) * 0.5
+    d = tmp_path / "whole"
+    info = bench.dump_outputs(str(d), x, 2.25)
+    got = np.load(d / "x.npy", allow_pickle=False)
+    assert got.dtype == np.float64 and np.array_equal(got, x) and not info["x"]["sampled"]
+    rr = np.load(d / "rr.npy", allow_pickle=False)
+    assert rr.dtype == np.float64 and rr.tolist() == [2.25]
+    assert (bench.DUMP_MAX_ELEMS + 1) * 8 <= 64 << 20  # x and rr together stay under 64 MB
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    samples = []
+    for name in ("s1", "s2"):
+        info = bench.dump_outputs(str(tmp_path / name), x, 2.25)
+        samples.append(np.load(tmp_path / name / "x.npy", allow_pickle=False))
+        assert info["x"] == {"elements": 64, "sampled": True}
+    assert samples[0].shape == (64,) and np.array_equal(samples[0], samples[1])
+    assert np.all(np.diff(samples[0]) >= 0) and set(samples[0]) <= set(x)
+
+
 def test_overlap_rule():
     import conjugate_gradient_amd as cg
     assert cg.overlap_rule({"overlap_form_us": 600.0, "plain_form_us": 620.0, "margin": 0.01})

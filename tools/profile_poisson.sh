@@ -5,7 +5,7 @@ set -euo pipefail
 export TMPDIR=/tmp
 OUT=gpurun_out
 mkdir -p $OUT
-timeout -k 10 300 python bench.py --workload poisson > $OUT/bench_poisson.json 2> $OUT/bench_poisson.err
+timeout -k 10 300 python bench.py --workload poisson --full > $OUT/bench_poisson.json 2> $OUT/bench_poisson.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_pois_kt -o kt --output-format csv -- \
     python bench.py --workload poisson --no-cpu > $OUT/bench_pois_kt.json 2> $OUT/bench_pois_kt.err
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/prof_pois_fetch -o fetch --output-format csv -- \
