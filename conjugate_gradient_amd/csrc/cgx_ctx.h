@@ -359,8 +359,16 @@ inline int64_t *rec_of(const cgx_ctx *c, const Shard &s, bool gated) {
     return (gated && &s == &c->sh[0]) ? s.d_rec : nullptr;
 }
 
+// Typed views of the shards' untyped device buffers and scalar slots.
+inline double *f64(void *p) { return static_cast<double *>(p); }
+inline const double *f64(const void *p) { return static_cast<const double *>(p); }
+inline float *f32(void *p) { return static_cast<float *>(p); }
+inline const float *f32(const void *p) { return static_cast<const float *>(p); }
+inline double *slot_f64(const Shard &s, int i) { return f64(slot(s, i)); }
+inline float *slot_f32(const Shard &s, int i) { return f32(slot(s, i)); }
+inline int64_t *slot_i64(const Shard &s, int i) { return static_cast<int64_t *>(slot(s, i)); }
 inline const int64_t *gate_of(const Shard &s, bool gated) {
-    return gated ? reinterpret_cast<const int64_t *>(slot(s, S_KDONE)) : nullptr;
+    return gated ? slot_i64(s, S_KDONE) : nullptr;
 }
 
 // roctx range over an API call (rocprofv3 --marker-trace shows the solve
@@ -386,8 +394,12 @@ int alloc_overlap(cgx_ctx *c);
 int finish_create(cgx_ctx *c, cgx_ctx **out);
 // cgx_exchange.hip
 int timing_resolve(cgx_ctx *c);
+// CGX_TIMING: one event pair on s.stream around a matVec of the first shard
+// (nothing on any other shard, or without the flag)
+int timing_begin(cgx_ctx *c, Shard &s);
+int timing_end(cgx_ctx *c, Shard &s);
 int phase_iter_begin(cgx_ctx *c);
-int64_t *ts_of(cgx_ctx *c, const Shard &s, int kern);
+int64_t *ts_of(const cgx_ctx *c, const Shard &s, int kern);
 void phase_iter_end(cgx_ctx *c);
 int phase_resolve(cgx_ctx *c);
 int progress_mark(cgx_ctx *c);
@@ -431,6 +443,16 @@ int do_iteration_poisson(cgx_ctx *c, double eps, int *stop, bool gated);
 int poisson_x_finish(cgx_ctx *c);
 int settle_rr(cgx_ctx *c);
 int check_x_complete(const cgx_ctx *c);
+// Row block s's two update launches of dense iteration k (after the matVec):
+// they only read the context (const: the row blocks' worker threads call
+// them, cgx_local_mt.hip).
+int launch_update_r(const cgx_ctx *c, const Shard &s, int64_t k, bool gated);
+enum XpForm {
+    XP_DECIDE,  // the kernel decides the stop, then updates x and p (gated)
+    XP_UPDATE,  // x and p, no decision (fixed count, or the host saw no stop)
+    XP_X_ONLY,  // x only: the host saw the stop
+};
+int launch_update_xp(const cgx_ctx *c, const Shard &s, int64_t k, XpForm form, double eps, bool fold_rr);
 int do_iteration(cgx_ctx *c, double eps, int *stop, bool gated = false);
 bool warm_eligible(const cgx_ctx *c);
 int warm_solve_kernels(cgx_ctx *c);

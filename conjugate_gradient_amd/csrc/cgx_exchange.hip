@@ -37,6 +37,22 @@ int timing_resolve(cgx_ctx *c) {
     return CGX_OK;
 }
 
+static bool timed_shard(const cgx_ctx *c, const Shard &s) { return (c->flags & CGX_TIMING) && &s == &c->sh[0]; }
+
+int timing_begin(cgx_ctx *c, Shard &s) {
+    if (!timed_shard(c, s)) return CGX_OK;
+    if (s.ev_used >= kEvPairs) TRY(timing_resolve(c));
+    HIPT(hipEventRecord(s.ev_t[2 * s.ev_used], s.stream));
+    return CGX_OK;
+}
+
+int timing_end(cgx_ctx *c, Shard &s) {
+    if (!timed_shard(c, s)) return CGX_OK;
+    HIPT(hipEventRecord(s.ev_t[2 * s.ev_used + 1], s.stream));
+    s.ev_used++;
+    return CGX_OK;
+}
+
 // ---- CGX_PHASES ------------------------------------------------------------------
 // The iteration's kernels on the first shard stamp their start and end on the
 // device's constant wall clock (cgx_kernels.h kTsSlot); nothing is inserted
@@ -55,7 +71,7 @@ int phase_iter_begin(cgx_ctx *c) {
     return CGX_OK;
 }
 
-int64_t *ts_of(cgx_ctx *c, const Shard &s, int kern) {
+int64_t *ts_of(const cgx_ctx *c, const Shard &s, int kern) {
     if (!(c->flags & CGX_PHASES) || &s != &c->sh[0] || s.ts_cur < 0) return nullptr;
     return s.ts_dev + ((size_t)s.ts_cur * kTsKern + kern) * kTsSlot;
 }
@@ -489,9 +505,6 @@ int exchange_scalar(cgx_ctx *c, int lslot, int gslot) {
     return CGX_OK;
 }
 
-// Where a kernel writes its (partial) scalar: the global slot directly when
-// there is nothing to combine, else the shard-local slot.
-
 // The overlapped matVec of row block d once p's exchange is enqueued on
 // d.cstream (the RCCL allgather, or the pull kernel): the own column block on
 // the compute stream (its p is local) while the exchange runs, then, once p
@@ -502,23 +515,17 @@ int exchange_scalar(cgx_ctx *c, int lslot, int gslot) {
 // for a second kernel's waves, so the two did not overlap, and the add cost
 // its launch; profiles/r05_rank_iteration.jsonl.  Removed.)
 int overlap_matvecs(cgx_ctx *c, Shard &d, int dot_slot, bool gated, bool timed) {
-    const double *A = reinterpret_cast<const double *>(d.A);
-    const double *v = reinterpret_cast<const double *>(d.pfull);
-    double *Ap = reinterpret_cast<double *>(d.Ap);
+    const double *A = f64(d.A);
+    const double *v = f64(d.pfull);
+    double *Ap = f64(d.Ap);
     HIPT(hipEventRecord(d.ev_gathered, d.cstream));
-    const bool timing = timed && (c->flags & CGX_TIMING) && (&d == &c->sh[0]);
-    if (timing && d.ev_used >= kEvPairs) TRY(timing_resolve(c));
-    if (timing) HIPT(hipEventRecord(d.ev_t[2 * d.ev_used], d.stream));
+    if (timed) TRY(timing_begin(c, d));
     HIPT(matvec_f64_cols(d.plan, A, c->lda, d.nloc, c->lda, d.row0, d.nloc, false, v, Ap, nullptr, nullptr, d.ws,
                          d.stream, gate_of(d, gated), ts_of(c, d, TK_OWN)));
     HIPT(hipStreamWaitEvent(d.stream, d.ev_gathered, 0));
     HIPT(matvec_f64_cols(d.plan, A, c->lda, d.nloc, c->lda, (d.row0 + d.nloc) % c->lda, c->lda - d.nloc, true, v, Ap,
-                         reinterpret_cast<const double *>(d.pown), reinterpret_cast<double *>(slot(d, dot_slot)),
-                         d.ws, d.stream, gate_of(d, gated), ts_of(c, d, TK_MV)));
-    if (timing) {
-        HIPT(hipEventRecord(d.ev_t[2 * d.ev_used + 1], d.stream));
-        d.ev_used++;
-    }
+                         f64(d.pown), slot_f64(d, dot_slot), d.ws, d.stream, gate_of(d, gated), ts_of(c, d, TK_MV)));
+    if (timed) TRY(timing_end(c, d));
     return CGX_OK;
 }
 

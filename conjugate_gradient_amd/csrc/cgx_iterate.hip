@@ -13,31 +13,52 @@ namespace cgxh {
 int matvec_rows(cgx_ctx *c, Shard &s, const MatvecPlan &pl, const char *Arows, int64_t r0, int64_t rows,
                 const char *vec, bool fuse_dot, int dot_slot, bool gated, int64_t *ts) {
     if (f32ref(c)) {
-        HIPT(matvec_ref_f32(reinterpret_cast<const float *>(Arows), c->lda, rows, c->n,
-                            reinterpret_cast<const float *>(vec), reinterpret_cast<float *>(s.Ap) + r0, s.stream,
-                            gate_of(s, gated)));
+        HIPT(matvec_ref_f32(f32(Arows), c->lda, rows, c->n, f32(vec), f32(s.Ap) + r0, s.stream, gate_of(s, gated)));
     } else if (c->rot && Arows == s.A && r0 == 0 && rows == s.nloc) {
         // the block's own columns, then the rest, summed apart and added: the
         // overlapped form's bits in one launch (cgx_ctx::rot)
-        HIPT(matvec_f64_cols(pl, reinterpret_cast<const double *>(Arows), c->lda, rows, c->lda, s.row0, c->lda, false,
-                             reinterpret_cast<const double *>(vec), reinterpret_cast<double *>(s.Ap),
-                             fuse_dot ? reinterpret_cast<const double *>(s.pown) : nullptr,
-                             fuse_dot ? reinterpret_cast<double *>(slot(s, dot_slot)) : nullptr, s.ws, s.stream,
-                             gated ? reinterpret_cast<const int64_t *>(slot(s, S_KDONE)) : nullptr, ts, s.nloc));
+        HIPT(matvec_f64_cols(pl, f64(Arows), c->lda, rows, c->lda, s.row0, c->lda, false, f64(vec), f64(s.Ap),
+                             fuse_dot ? f64(s.pown) : nullptr, fuse_dot ? slot_f64(s, dot_slot) : nullptr, s.ws,
+                             s.stream, gate_of(s, gated), ts, s.nloc));
     } else {
-        HIPT(matvec_f64(pl, reinterpret_cast<const double *>(Arows), c->lda, rows, c->lda,
-                        reinterpret_cast<const double *>(vec), reinterpret_cast<double *>(s.Ap) + r0,
-                        fuse_dot ? reinterpret_cast<const double *>(s.pown) + r0 : nullptr,
-                        fuse_dot ? reinterpret_cast<double *>(slot(s, dot_slot)) : nullptr, s.ws, s.stream,
-                        gated ? reinterpret_cast<const int64_t *>(slot(s, S_KDONE)) : nullptr, ts));
+        HIPT(matvec_f64(pl, f64(Arows), c->lda, rows, c->lda, f64(vec), f64(s.Ap) + r0,
+                        fuse_dot ? f64(s.pown) + r0 : nullptr, fuse_dot ? slot_f64(s, dot_slot) : nullptr, s.ws,
+                        s.stream, gate_of(s, gated), ts));
     }
     return CGX_OK;
 }
 
-// CGX_HOST_STREAM matVec: tile t goes to buffer (next_buf++ % kStreamBufs);
-// its copy waits until the kernel that last read that buffer is done (A is
-// read-only, so copies of the next iteration's first tiles overlap this
-// iteration's vector work); its kernel waits for the copy.
+// CGX_HOST_STREAM: the part of A that is not resident, `units` units of
+// `unit_bytes` each at A_host (rows, or CGX_SYMMETRIC's tiles), from unit
+// res_rows on in chunks of tile_rows.  Chunk t goes to buffer
+// (next_buf++ % kStreamBufs); its copy waits until the kernel that last read
+// that buffer is done (A is read-only, so copies of the next iteration's first
+// chunks overlap this iteration's vector work); launch(buffer, first unit,
+// count) enqueues its kernel on the compute stream, which waits for the copy.
+template <class Launch>
+static int stream_chunks(Shard &s, int64_t unit_bytes, int64_t units, Launch launch) {
+    for (int64_t u0 = s.res_rows; u0 < units; u0 += s.tile_rows) {
+        const int64_t cnt = std::min(s.tile_rows, units - u0);
+        const int b = s.next_buf;
+        s.next_buf = (s.next_buf + 1) % kStreamBufs;
+        const int64_t bytes = cnt * unit_bytes;
+        const char *src = s.A_host + (size_t)u0 * unit_bytes;
+        const int64_t part = (bytes / s.ncopy + 4095) & ~int64_t(4095);
+        for (int q = 0; q < s.ncopy; ++q) {
+            const int64_t lo = std::min<int64_t>(bytes, q * part), hi = std::min<int64_t>(bytes, lo + part);
+            if (s.buf_used[b]) HIPT(hipStreamWaitEvent(s.copy[q], s.ev_free[b], 0));
+            if (hi > lo) HIPT(hipMemcpyAsync(s.tile[b] + lo, src + lo, hi - lo, hipMemcpyHostToDevice, s.copy[q]));
+            HIPT(hipEventRecord(s.ev_loaded[b][q], s.copy[q]));
+            HIPT(hipStreamWaitEvent(s.stream, s.ev_loaded[b][q], 0));
+        }
+        TRY(launch(s.tile[b], u0, cnt));
+        HIPT(hipEventRecord(s.ev_free[b], s.stream));
+        s.buf_used[b] = true;
+    }
+    return CGX_OK;
+}
+
+// CGX_HOST_STREAM matVec (stream_chunks).
 // With resident rows (CGX_STREAM_RESIDENT_MB) their kernel goes first on the
 // compute stream, so it runs while the copy streams bring in the first tiles
 // of the rest (same row sums: every plan adds a row in the same order).
@@ -50,111 +71,60 @@ int matvec_streamed(cgx_ctx *c, Shard &s, const char *vec) {
         }
         TRY(matvec_rows(c, s, s.res_plan, s.A, 0, s.res_rows, vec, false, 0));
     }
-    for (int64_t r0 = s.res_rows; r0 < s.nloc; r0 += s.tile_rows) {
-        const int64_t rows = std::min(s.tile_rows, s.nloc - r0);
-        const int b = s.next_buf;
-        s.next_buf = (s.next_buf + 1) % kStreamBufs;
-        const int64_t bytes = rows * row_bytes;
-        const char *src = s.A_host + (size_t)r0 * row_bytes;
-        const int64_t part = (bytes / s.ncopy + 4095) & ~int64_t(4095);
-        for (int q = 0; q < s.ncopy; ++q) {
-            const int64_t lo = std::min<int64_t>(bytes, q * part), hi = std::min<int64_t>(bytes, lo + part);
-            if (s.buf_used[b]) HIPT(hipStreamWaitEvent(s.copy[q], s.ev_free[b], 0));
-            if (hi > lo) HIPT(hipMemcpyAsync(s.tile[b] + lo, src + lo, hi - lo, hipMemcpyHostToDevice, s.copy[q]));
-            HIPT(hipEventRecord(s.ev_loaded[b][q], s.copy[q]));
-            HIPT(hipStreamWaitEvent(s.stream, s.ev_loaded[b][q], 0));
-        }
-        TRY(matvec_rows(c, s, s.tile_plan, s.tile[b], r0, rows, vec, false, 0));
-        HIPT(hipEventRecord(s.ev_free[b], s.stream));
-        s.buf_used[b] = true;
-    }
-    return CGX_OK;
+    return stream_chunks(s, row_bytes, s.nloc, [&](const char *tile, int64_t r0, int64_t rows) {
+        return matvec_rows(c, s, s.tile_plan, tile, r0, rows, vec, false, 0);
+    });
 }
 
 // CGX_SYMMETRIC | CGX_HOST_STREAM: the upper-triangle tiles stream from
-// pinned host memory in chunks (the same buffer rotation and copy streams as
-// matvec_streamed); each chunk's k_symv_f64 writes per-tile row and column
-// partials, and one reduce (with the fused p.Ap) follows the last chunk.
+// pinned host memory in chunks (stream_chunks, as matvec_streamed's rows);
+// each chunk's k_symv_f64 writes per-tile row and column partials, and one
+// reduce (with the fused p.Ap) follows the last chunk.
 int matvec_sym_streamed(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, int dot_slot, const int64_t *gate) {
     const int64_t ntiles = sym_tiles(c->lda), tb = 128 * 128 * 8;
-    const double *p = reinterpret_cast<const double *>(vec);
+    auto tiles = [&](const char *At, int64_t q0, int64_t cnt) {
+        HIPT(symv_tiles_f64(f64(At), q0, cnt, c->lda, s.sym_grid, true, f64(vec), f64(s.sym_prow), f64(s.sym_pcol),
+                            s.stream, gate));
+        return (int)CGX_OK;
+    };
     if (s.res_rows > 0) {  // the resident tiles first, under the copies of the rest (as matvec_streamed)
         if (s.res_dirty) {
             HIPT(hipMemcpyAsync(s.A, s.A_host, (size_t)s.res_rows * tb, hipMemcpyHostToDevice, s.stream));
             s.res_dirty = false;
         }
-        HIPT(symv_tiles_f64(reinterpret_cast<const double *>(s.A), 0, s.res_rows, c->lda, s.sym_grid, true, p,
-                            reinterpret_cast<double *>(s.sym_prow), reinterpret_cast<double *>(s.sym_pcol), s.stream,
-                            gate));
+        TRY(tiles(s.A, 0, s.res_rows));
     }
-    for (int64_t q0 = s.res_rows; q0 < ntiles; q0 += s.tile_rows) {
-        const int64_t cnt = std::min(s.tile_rows, ntiles - q0);
-        const int b = s.next_buf;
-        s.next_buf = (s.next_buf + 1) % kStreamBufs;
-        const int64_t bytes = cnt * tb;
-        const char *src = s.A_host + (size_t)q0 * tb;
-        const int64_t part = (bytes / s.ncopy + 4095) & ~int64_t(4095);
-        for (int q = 0; q < s.ncopy; ++q) {
-            const int64_t lo = std::min<int64_t>(bytes, q * part), hi = std::min<int64_t>(bytes, lo + part);
-            if (s.buf_used[b]) HIPT(hipStreamWaitEvent(s.copy[q], s.ev_free[b], 0));
-            if (hi > lo) HIPT(hipMemcpyAsync(s.tile[b] + lo, src + lo, hi - lo, hipMemcpyHostToDevice, s.copy[q]));
-            HIPT(hipEventRecord(s.ev_loaded[b][q], s.copy[q]));
-            HIPT(hipStreamWaitEvent(s.stream, s.ev_loaded[b][q], 0));
-        }
-        HIPT(symv_tiles_f64(reinterpret_cast<const double *>(s.tile[b]), q0, cnt, c->lda, s.sym_grid, true, p,
-                            reinterpret_cast<double *>(s.sym_prow), reinterpret_cast<double *>(s.sym_pcol), s.stream,
-                            gate));
-        HIPT(hipEventRecord(s.ev_free[b], s.stream));
-        s.buf_used[b] = true;
-    }
-    HIPT(symv_reduce_f64(c->n, c->lda, 1, reinterpret_cast<const double *>(s.sym_prow),
-                         reinterpret_cast<const double *>(s.sym_pcol), reinterpret_cast<double *>(s.Ap),
-                         with_dot ? reinterpret_cast<const double *>(s.pown) : nullptr,
-                         with_dot ? reinterpret_cast<double *>(slot(s, dot_slot)) : nullptr, s.ws, s.stream, gate));
+    TRY(stream_chunks(s, tb, ntiles, tiles));
+    HIPT(symv_reduce_f64(c->n, c->lda, 1, f64(s.sym_prow), f64(s.sym_pcol), f64(s.Ap),
+                         with_dot ? f64(s.pown) : nullptr, with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream,
+                         gate));
     return CGX_OK;
 }
 
-// The host-mapped convergence record: written by shard 0's deciding kernel only.
-
 int launch_matvec(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, int dot_slot, bool gated) {
-    const bool timing = (c->flags & CGX_TIMING) && (&s == &c->sh[0]);
-    if (timing && s.ev_used >= kEvPairs) TRY(timing_resolve(c));
-    if (timing) HIPT(hipEventRecord(s.ev_t[2 * s.ev_used], s.stream));
+    TRY(timing_begin(c, s));
     const bool streamed = (c->flags & CGX_HOST_STREAM) != 0;
     if (c->op == OP_POISSON)
-        HIPT(stencil5_f64(reinterpret_cast<const double *>(vec), s.nloc / c->m, c->m, reinterpret_cast<double *>(s.Ap),
-                          with_dot ? reinterpret_cast<double *>(slot(s, dot_slot)) : nullptr, s.ws, s.stream,
-                          gate_of(s, gated)));
+        HIPT(stencil5_f64(f64(vec), s.nloc / c->m, c->m, f64(s.Ap), with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws,
+                          s.stream, gate_of(s, gated)));
     else if (streamed && (c->flags & CGX_SYMMETRIC))
         TRY(matvec_sym_streamed(c, s, vec, with_dot, dot_slot, gate_of(s, gated)));
     else if (streamed) TRY(matvec_streamed(c, s, vec));
     else if (c->flags & CGX_SYMMETRIC)
-        HIPT(symv_f64(reinterpret_cast<const double *>(s.A), c->n, c->lda, s.sym_grid,
-                      reinterpret_cast<const double *>(vec), reinterpret_cast<double *>(s.sym_prow),
-                      reinterpret_cast<double *>(s.sym_pcol), reinterpret_cast<double *>(s.Ap),
-                      with_dot ? reinterpret_cast<const double *>(s.pown) : nullptr,
-                      with_dot ? reinterpret_cast<double *>(slot(s, dot_slot)) : nullptr, s.ws, s.stream,
+        HIPT(symv_f64(f64(s.A), c->n, c->lda, s.sym_grid, f64(vec), f64(s.sym_prow), f64(s.sym_pcol), f64(s.Ap),
+                      with_dot ? f64(s.pown) : nullptr, with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream,
                       gate_of(s, gated)));
     else if (with_dot && c->ref_mv_dot)  // matVec + vecVec(p, Ap) in one launch (serialConjugate.c:215,219)
-        HIPT(matvec_dot_ref_f32(reinterpret_cast<const float *>(s.A), c->lda, s.nloc, c->n,
-                                reinterpret_cast<const float *>(vec), reinterpret_cast<float *>(s.Ap),
-                                reinterpret_cast<const float *>(s.pown), reinterpret_cast<float *>(slot(s, dot_slot)),
-                                s.ws.tickets + T_REF_MV, s.stream, gate_of(s, gated)));
+        HIPT(matvec_dot_ref_f32(f32(s.A), c->lda, s.nloc, c->n, f32(vec), f32(s.Ap), f32(s.pown),
+                                slot_f32(s, dot_slot), s.ws.tickets + T_REF_MV, s.stream, gate_of(s, gated)));
     else TRY(matvec_rows(c, s, s.plan, s.A, 0, s.nloc, vec, with_dot && !f32ref(c), dot_slot, gated,
                          f32ref(c) ? nullptr : ts_of(c, s, TK_MV)));
-    if (timing) {
-        HIPT(hipEventRecord(s.ev_t[2 * s.ev_used + 1], s.stream));
-        s.ev_used++;
-    }
+    TRY(timing_end(c, s));
     if (with_dot && ((f32ref(c) && !c->ref_mv_dot) || (streamed && !(c->flags & CGX_SYMMETRIC)))) {
         if (f32ref(c))  // vecVec(p, Ap) sequential (serialConjugate.c:219)
-            HIPT(dot_ref_f32(s.nloc, reinterpret_cast<const float *>(s.pown),
-                             reinterpret_cast<const float *>(s.Ap), reinterpret_cast<float *>(slot(s, dot_slot)),
-                             s.stream, gate_of(s, gated)));
+            HIPT(dot_ref_f32(s.nloc, f32(s.pown), f32(s.Ap), slot_f32(s, dot_slot), s.stream, gate_of(s, gated)));
         else
-            HIPT(dot_f64(s.nloc, reinterpret_cast<const double *>(s.pown),
-                         reinterpret_cast<const double *>(s.Ap), reinterpret_cast<double *>(slot(s, dot_slot)), s.ws,
-                         s.stream));
+            HIPT(dot_f64(s.nloc, f64(s.pown), f64(s.Ap), slot_f64(s, dot_slot), s.ws, s.stream));
     }
     return CGX_OK;
 }
@@ -179,6 +149,19 @@ int x0_is_zero(cgx_ctx *c, bool *zero) {
     TRY(rank_wait_stream(c, s.stream, "the x0 check"));
     *zero = pin[0] == 0;
     return CGX_OK;
+}
+
+// The host's record of a solve at its start: do_begin's (ST_BEGUN), and what
+// the creation warm-up goes back to (ST_IDLE, warm_solve_kernels).
+// total_iters and last_rr outlive a solve and are not touched here.
+static void reset_solve_state(cgx_ctx *c, State st) {
+    for (auto &s : c->sh) s.h_rec[0] = s.h_rec[1] = 0;
+    c->k = 0;
+    c->converged = 0;
+    c->state = st;
+    c->x_incomplete = c->x_deferred = false;
+    c->xalpha_pending = false;
+    c->iter_failed = false;
 }
 
 int do_begin(cgx_ctx *c) {
@@ -225,13 +208,7 @@ int do_begin(cgx_ctx *c) {
     if (c->fused && !c->halo_pull) TRY(exchange_halo_of(c, &Shard::rh));
     // The device-side convergence record {kdone, r.r} was reset by the residual
     // kernel above (k_residual_f64 / k_dot_ref_f32_blk<kDotResid>); the host copy here.
-    for (auto &s : c->sh) s.h_rec[0] = s.h_rec[1] = 0;  // no kernel of this solve has run yet (do_begin follows a sync)
-    c->k = 0;
-    c->converged = 0;
-    c->state = ST_BEGUN;
-    c->x_incomplete = c->x_deferred = false;
-    c->xalpha_pending = false;
-    c->iter_failed = false;
+    reset_solve_state(c, ST_BEGUN);  // no kernel of this solve has run yet (do_begin follows a sync)
     return CGX_OK;
 }
 
@@ -250,6 +227,22 @@ int read_scalar(cgx_ctx *c, int gslot, double *out) {
     return CGX_OK;
 }
 
+// The host-checked stop after iteration c->k - 1, whose r.r is in slot rg:
+// if (sqrt(beta) < EPSILON) break;  serialConjugate.c:235-238.  eps < 0
+// (fixed count): nothing is read back.
+static int host_check_stop(cgx_ctx *c, int rg, double eps, int *stop) {
+    if (eps < 0.0) return CGX_OK;
+    double rr = 0.0;
+    TRY(read_scalar(c, rg, &rr));
+    c->last_rr = rr;
+    if (std::sqrt(rr) < eps) {
+        c->converged = 1;
+        c->state = ST_CONVERGED;
+        *stop = 1;
+    }
+    return CGX_OK;
+}
+
 // Fused Poisson iteration k (conjgrad.m's loop, two kernels, 64 B per grid
 // point; see k_poisson_p_f64 / k_poisson_xr_f64):
 //   p_k = r_k + beta p_{k-1}, p_k . A p_k      (gated: first decides the
@@ -257,9 +250,9 @@ int read_scalar(cgx_ctx *c, int gslot, double *out) {
 //   allreduce(p.Ap)
 //   x += alpha p_k, r -= alpha A p_k, r.r
 //   allreduce(r.r); host-checked stop; r's halo rows for the next iteration.
-// x is updated every other iteration (c->xdefer: the left-out iteration's
-// alpha is kept in S_XALPHA and p_k stays in its slab until the next
-// iteration's xr kernel has read it); poisson_x_finish completes it at the end
+// x is updated every c->xd-th iteration (c->xd > 1: a left-out iteration's
+// alpha is kept in S_XALPHA + j and its p_k stays in its slab until the
+// catching-up xr kernel has read it); poisson_x_finish completes it at the end
 // of a cgx_iterate call.
 // Where p_k lives: two slabs alternate (pfull for even k), three rotate with x every third iteration.
 static char *poisson_slab(const cgx_ctx *c, const Shard &s, int64_t k) {
@@ -276,7 +269,6 @@ int do_iteration_poisson(cgx_ctx *c, double eps, int *stop, bool gated) {
     const int64_t m = c->m;
     const int pg = S_PAP + ring(k), pl = S_LPAP + ring(k);
     const int rk = S_RR + ring(k), rkm1 = S_RR + ring(k + 3);  // r.r of iterations k, k-1
-    auto D = [](void *p) { return reinterpret_cast<double *>(p); };
     const bool split = c->halo_pending;  // interior runs while the r halo exchange is in flight
     // x every D-th iteration (D = c->xd): leave it out at the first D-1 of every
     // D iterations from k0 (alpha_k to slot S_XALPHA + j), catch up at the D-th
@@ -297,16 +289,15 @@ int do_iteration_poisson(cgx_ctx *c, double eps, int *stop, bool gated) {
         TRY(set_dev(s));
         char *pold = poisson_slab(c, s, k - 1), *pnew = poisson_slab(c, s, k);
         // the previous slab's last interior row of r, the next slab's first
-        const double *r_up = c->halo_pull && q > 0 ? D(c->sh[q - 1].rh) + mloc * m : nullptr;
-        const double *r_dn = c->halo_pull && q < S - 1 ? D(c->sh[q + 1].r) : nullptr;
+        const double *r_up = c->halo_pull && q > 0 ? f64(c->sh[q - 1].rh) + mloc * m : nullptr;
+        const double *r_dn = c->halo_pull && q < S - 1 ? f64(c->sh[q + 1].r) : nullptr;
         const PeerSum rs = c->rr_unsummed ? peer_sum(c, s, S_LRR + ring(k), rk) : PeerSum{};
         for (int part : split ? std::initializer_list<int>{1, 2} : std::initializer_list<int>{0}) {
             if (part == 2) HIPT(hipStreamWaitEvent(s.stream, s.ev_gathered, 0));
-            HIPT(poisson_p_f64(D(s.rh), D(pold), D(pnew), mloc, m, D(slot(s, rk)), D(slot(s, rkm1)), k == 0,
-                               D(slot(s, out_slot(c, pl, pg))), s.ws, s.stream, gated ? eps : -1.0, k,
-                               gated ? reinterpret_cast<int64_t *>(slot(s, S_KDONE)) : nullptr,
-                               gated ? D(slot(s, S_RRFINAL)) : nullptr, part, rec_of(c, s, gated), r_up, r_dn,
-                               c->rr_unsummed ? &rs : nullptr));
+            HIPT(poisson_p_f64(f64(s.rh), f64(pold), f64(pnew), mloc, m, slot_f64(s, rk), slot_f64(s, rkm1), k == 0,
+                               slot_f64(s, out_slot(c, pl, pg)), s.ws, s.stream, gated ? eps : -1.0, k,
+                               gated ? slot_i64(s, S_KDONE) : nullptr, gated ? slot_f64(s, S_RRFINAL) : nullptr, part,
+                               rec_of(c, s, gated), r_up, r_dn, c->rr_unsummed ? &rs : nullptr));
         }
     }
     c->rr_unsummed = false;
@@ -317,19 +308,14 @@ int do_iteration_poisson(cgx_ctx *c, double eps, int *stop, bool gated) {
     const int ro = out_slot(c, rl, rg);
     for (auto &s : c->sh) {
         TRY(set_dev(s));
-        const bool timing = (c->flags & CGX_TIMING) && (&s == &c->sh[0]);
-        if (timing && s.ev_used >= kEvPairs) TRY(timing_resolve(c));
-        if (timing) HIPT(hipEventRecord(s.ev_t[2 * s.ev_used], s.stream));
+        TRY(timing_begin(c, s));
         char *pnew = poisson_slab(c, s, k), *pold = poisson_slab(c, s, k - 1),
              *pq = c->xd == 3 ? poisson_slab(c, s, k - 2) : nullptr;
         const PeerSum ps = c->fuse_combine ? peer_sum(c, s, pl, pg) : PeerSum{};
-        HIPT(poisson_xr_f64(D(pnew), D(pold), D(pq), D(s.x), D(s.r), mloc, m, D(slot(s, rk)), D(slot(s, pg)),
-                            D(slot(s, ro)), xmode, D(slot(s, xslot)), s.ws, s.stream, gate_of(s, gated),
-                            c->fuse_combine ? &ps : nullptr));
-        if (timing) {
-            HIPT(hipEventRecord(s.ev_t[2 * s.ev_used + 1], s.stream));
-            s.ev_used++;
-        }
+        HIPT(poisson_xr_f64(f64(pnew), f64(pold), f64(pq), f64(s.x), f64(s.r), mloc, m, slot_f64(s, rk),
+                            slot_f64(s, pg), slot_f64(s, ro), xmode, slot_f64(s, xslot), s.ws, s.stream,
+                            gate_of(s, gated), c->fuse_combine ? &ps : nullptr));
+        TRY(timing_end(c, s));
     }
     c->xalpha_pending = xmode == 0;  // the catch-up (xmode xd) and every-iteration x (1) leave nothing out
     if (fold_rr) {  // MPI_Allreduce(r.r): summed by the next k_poisson_p (or settle_rr)
@@ -340,17 +326,8 @@ int do_iteration_poisson(cgx_ctx *c, double eps, int *stop, bool gated) {
     }
     c->k = k + 1;
     c->total_iters += 1;
-    if (!gated && eps >= 0.0) {
-        double rr = 0.0;
-        TRY(read_scalar(c, rg, &rr));
-        c->last_rr = rr;
-        if (std::sqrt(rr) < eps) {
-            c->converged = 1;
-            c->state = ST_CONVERGED;
-            *stop = 1;
-            return CGX_OK;
-        }
-    }
+    if (!gated) TRY(host_check_stop(c, rg, eps, stop));
+    if (*stop) return CGX_OK;  // before the halo exchange: no next iteration reads r
     if (c->halo_pull) return CGX_OK;  // the next k_poisson_p reads the neighbours' rows itself
     return c->halo_overlap ? exchange_halo_async(c) : exchange_halo_of(c, &Shard::rh);
 }
@@ -398,93 +375,50 @@ int check_x_complete(const cgx_ctx *c) {
                                "and is incomplete until cgx_set_x or the next cgx_solve_begin", (long long)c->k);
 }
 
-// One loop iteration k (serialConjugate.c:215-244 / parallel_cg.c:290-323).
-// Returns 1 in *stop when sqrt(r.r) < eps ended the loop (before the p update,
-// as the reference breaks at :235-238).
-// gated: fp64 device-side convergence (the host does not read r.r here; the
-// update kernel decides sqrt(r.r) < eps and later kernels skip themselves).
-// The two-launch iteration of a small dense fp64 system on one GPU
-// (c->fused_p): the matVec with its fused p.Ap, then k_update_xrp_f64, whose
-// last block decides the stop and forms p for the next iteration.  The same
-// expressions in the same order as the three launches below (bitwise the same
-// x), one kernel boundary and one host launch fewer per iteration.
-static int do_iteration_fused_p(cgx_ctx *c, double eps, int *stop, bool gated) {
-    const int64_t k = c->k;
-    *stop = 0;
-    Shard &s = c->sh[0];
-    const int pg = S_PAP + ring(k), rg = S_RR + ring(k + 1);
-    auto D = [](void *q) { return reinterpret_cast<double *>(q); };
-    TRY(phase_iter_begin(c));
+// ---- one GPU, two launches per iteration --------------------------------------------
+// Each form below is its matVec launch and its update launch, with p.Ap in
+// slot pg and the new r.r in slot rg; do_iteration_two_launch is the frame
+// they share.
+//
+// A small dense fp64 system (c->fused_p): the matVec with its fused p.Ap, then
+// k_update_xrp_f64, whose last block decides the stop and forms p for the next
+// iteration.  The same expressions in the same order as do_iteration's three
+// launches (bitwise the same x), one kernel boundary and one host launch fewer
+// per iteration.
+static int launch_fused_p(cgx_ctx *c, Shard &s, int64_t k, int pg, int rg, double eps, bool gated) {
     TRY(launch_matvec(c, s, s.pfull, true, pg, gated));  // serialConjugate.c:215,219
-    HIPT(update_xrp_f64(s.nloc, D(s.x), D(s.r), D(s.pown), D(s.Ap), D(slot(s, S_RR + ring(k))), D(slot(s, pg)),
-                        D(slot(s, rg)), s.ws, s.stream, gate_of(s, gated), gated ? eps : -1.0, k,
-                        gated ? reinterpret_cast<int64_t *>(slot(s, S_KDONE)) : nullptr,
-                        gated ? D(slot(s, S_RRFINAL)) : nullptr, rec_of(c, s, gated), ts_of(c, s, TK_UXP)));  // :221-243
-    phase_iter_end(c);
-    c->k = k + 1;
-    c->total_iters += 1;
-    if (!gated && eps >= 0.0) {  // host-checked stop; x is already current
-        double rr = 0.0;
-        TRY(read_scalar(c, rg, &rr));
-        c->last_rr = rr;
-        if (std::sqrt(rr) < eps) {
-            c->converged = 1;
-            c->state = ST_CONVERGED;
-            *stop = 1;
-        }
-    }
+    HIPT(update_xrp_f64(s.nloc, f64(s.x), f64(s.r), f64(s.pown), f64(s.Ap), slot_f64(s, S_RR + ring(k)),
+                        slot_f64(s, pg), slot_f64(s, rg), s.ws, s.stream, gate_of(s, gated), gated ? eps : -1.0, k,
+                        gated ? slot_i64(s, S_KDONE) : nullptr, gated ? slot_f64(s, S_RRFINAL) : nullptr,
+                        rec_of(c, s, gated), ts_of(c, s, TK_UXP)));  // :221-243
     return CGX_OK;
 }
 
-// The two-launch iteration with the p update folded into the matVec
-// (c->fold_p): k_matvec_fold_f64 forms p_k = r_k + beta p_{k-1} as it
+// ... with the p update folded into the matVec (c->fold_p):
+// k_matvec_fold_f64 forms p_k = r_k + beta p_{k-1} as it
 // multiplies it (its row owners store p_k into the other p buffer and fuse
 // p_k . A p_k), then k_update_xr_stop_f64 does x, r, r.r and the stopping
 // decision on every block -- no single-block pass over p.  Iteration 0 uses
 // p_0 = r_0 as the residual left it.  p_k lives in pfull for even k, in
 // p_alt for odd k.  The expressions are the three-launch kernels' (bitwise
 // the same x, test_two_launch_iteration_bitwise_equals_three).
-static int do_iteration_fold_p(cgx_ctx *c, double eps, int *stop, bool gated) {
-    const int64_t k = c->k;
-    *stop = 0;
-    Shard &s = c->sh[0];
-    const int pg = S_PAP + ring(k), rg = S_RR + ring(k + 1);
-    auto D = [](void *q) { return reinterpret_cast<double *>(q); };
+static int launch_fold_p(cgx_ctx *c, Shard &s, int64_t k, int pg, int rg, double eps, bool gated) {
     char *pk = (k & 1) ? s.p_alt : s.pfull, *pkm1 = (k & 1) ? s.pfull : s.p_alt;
-    TRY(phase_iter_begin(c));
     if (k == 0) {
         TRY(launch_matvec(c, s, s.pfull, true, pg, gated));  // serialConjugate.c:215,219 with p_0 = r_0
     } else {
-        const bool timing = (c->flags & CGX_TIMING) != 0;
-        if (timing && s.ev_used >= kEvPairs) TRY(timing_resolve(c));
-        if (timing) HIPT(hipEventRecord(s.ev_t[2 * s.ev_used], s.stream));
+        TRY(timing_begin(c, s));
         // every column up to lda, as the plain matVec runs them (A, r and both p
         // buffers are zero there), so the row sums add in the same order
-        HIPT(matvec_fold_f64(s.fold_plan, D(s.A), c->lda, s.nloc, c->lda, D(s.r), D(pkm1), D(pk), D(slot(s, S_RR + ring(k))),
-                             D(slot(s, S_RR + ring(k + 3))), D(s.Ap), D(slot(s, pg)), s.ws, s.stream,
-                             gate_of(s, gated), ts_of(c, s, TK_MV)));  // :239-243 of k-1, then :215,219
-        if (timing) {
-            HIPT(hipEventRecord(s.ev_t[2 * s.ev_used + 1], s.stream));
-            s.ev_used++;
-        }
+        HIPT(matvec_fold_f64(s.fold_plan, f64(s.A), c->lda, s.nloc, c->lda, f64(s.r), f64(pkm1), f64(pk),
+                             slot_f64(s, S_RR + ring(k)), slot_f64(s, S_RR + ring(k + 3)), f64(s.Ap), slot_f64(s, pg),
+                             s.ws, s.stream, gate_of(s, gated), ts_of(c, s, TK_MV)));  // :239-243 of k-1, then :215,219
+        TRY(timing_end(c, s));
     }
-    HIPT(update_xr_stop_f64(s.nloc, D(s.x), D(s.r), D(pk), D(s.Ap), D(slot(s, S_RR + ring(k))), D(slot(s, pg)),
-                            D(slot(s, rg)), s.ws, s.stream, gate_of(s, gated), gated ? eps : -1.0, k,
-                            gated ? reinterpret_cast<int64_t *>(slot(s, S_KDONE)) : nullptr,
-                            gated ? D(slot(s, S_RRFINAL)) : nullptr, rec_of(c, s, gated), ts_of(c, s, TK_UXP)));
-    phase_iter_end(c);
-    c->k = k + 1;
-    c->total_iters += 1;
-    if (!gated && eps >= 0.0) {  // host-checked stop; x is already current
-        double rr = 0.0;
-        TRY(read_scalar(c, rg, &rr));
-        c->last_rr = rr;
-        if (std::sqrt(rr) < eps) {
-            c->converged = 1;
-            c->state = ST_CONVERGED;
-            *stop = 1;
-        }
-    }
+    HIPT(update_xr_stop_f64(s.nloc, f64(s.x), f64(s.r), f64(pk), f64(s.Ap), slot_f64(s, S_RR + ring(k)),
+                            slot_f64(s, pg), slot_f64(s, rg), s.ws, s.stream, gate_of(s, gated), gated ? eps : -1.0,
+                            k, gated ? slot_i64(s, S_KDONE) : nullptr, gated ? slot_f64(s, S_RRFINAL) : nullptr,
+                            rec_of(c, s, gated), ts_of(c, s, TK_UXP)));
     return CGX_OK;
 }
 
@@ -492,38 +426,88 @@ static int do_iteration_fold_p(cgx_ctx *c, double eps, int *stop, bool gated) {
 // vecVec(p, Ap), then one single-block launch for x += p alpha, r -= Ap alpha,
 // r.r, the stopping test and p = r + p (rr/rsold) -- four launches' float
 // operations in their order (bitwise the same x and loop count).
-static int do_iteration_ref_fused(cgx_ctx *c, double eps, int *stop, bool gated) {
+static int launch_ref_fused(cgx_ctx *c, Shard &s, int64_t k, int pg, int rg, double eps, bool gated) {
+    TRY(launch_matvec(c, s, s.pfull, true, pg, gated));  // serialConjugate.c:215,219
+    HIPT(update_xrp_dot_ref_f32(s.nloc, f32(s.x), f32(s.r), f32(s.pown), f32(s.Ap), slot_f32(s, S_RR + ring(k)),
+                                slot_f32(s, pg), slot_f32(s, rg), s.stream, gate_of(s, gated), gated ? eps : -1.0, k,
+                                gated ? slot_i64(s, S_KDONE) : nullptr, gated ? slot_f64(s, S_RRFINAL) : nullptr,
+                                rec_of(c, s, gated)));  // :220-243
+    return CGX_OK;
+}
+
+static int do_iteration_two_launch(cgx_ctx *c, double eps, int *stop, bool gated) {
     const int64_t k = c->k;
     *stop = 0;
     Shard &s = c->sh[0];
     const int pg = S_PAP + ring(k), rg = S_RR + ring(k + 1);
-    auto F = [](void *q) { return reinterpret_cast<float *>(q); };
-    TRY(launch_matvec(c, s, s.pfull, true, pg, gated));  // serialConjugate.c:215,219
-    HIPT(update_xrp_dot_ref_f32(s.nloc, F(s.x), F(s.r), F(s.pown), F(s.Ap), F(slot(s, S_RR + ring(k))),
-                                F(slot(s, pg)), F(slot(s, rg)), s.stream, gate_of(s, gated), gated ? eps : -1.0, k,
-                                gated ? reinterpret_cast<int64_t *>(slot(s, S_KDONE)) : nullptr,
-                                gated ? reinterpret_cast<double *>(slot(s, S_RRFINAL)) : nullptr,
-                                rec_of(c, s, gated)));  // :220-243
+    const bool phases = !c->ref_fused;  // the F32_REF kernels stamp no phases
+    if (phases) TRY(phase_iter_begin(c));
+    if (c->fold_p) TRY(launch_fold_p(c, s, k, pg, rg, eps, gated));
+    else if (c->fused_p) TRY(launch_fused_p(c, s, k, pg, rg, eps, gated));
+    else TRY(launch_ref_fused(c, s, k, pg, rg, eps, gated));
+    if (phases) phase_iter_end(c);
     c->k = k + 1;
     c->total_iters += 1;
-    if (!gated && eps >= 0.0) {  // host-checked stop; x is already current
-        double rr = 0.0;
-        TRY(read_scalar(c, rg, &rr));
-        c->last_rr = rr;
-        if (std::sqrt(rr) < eps) {
-            c->converged = 1;
-            c->state = ST_CONVERGED;
-            *stop = 1;
-        }
+    if (!gated) TRY(host_check_stop(c, rg, eps, stop));  // x is already current
+    return CGX_OK;
+}
+
+// ---- the row blocks' update launches ---------------------------------------------------
+// Row block s, iteration k, after the p.Ap combine (or its barrier, when the
+// kernel sums the partials itself: fuse_combine / fuse_f32).
+int launch_update_r(const cgx_ctx *c, const Shard &s, int64_t k, bool gated) {
+    const int pg = S_PAP + ring(k), pl = S_LPAP + ring(k), rk = S_RR + ring(k);
+    const int ro = out_slot(c, S_LRR + ring(k + 1), S_RR + ring(k + 1));
+    if (f32ref(c)) {
+        // x += alpha p; r -= alpha Ap; r.r in one launch  (serialConjugate.c:219-234)
+        const PeerSumF32 ps = c->fuse_f32 ? peer_sum_f32(c, s, pl, pg) : PeerSumF32{};
+        HIPT(update_xr_dot_ref_f32(s.nloc, f32(s.x), f32(s.r), f32(s.pown), f32(s.Ap), slot_f32(s, rk),
+                                   slot_f32(s, pg), slot_f32(s, ro), s.stream, gate_of(s, gated),
+                                   c->fuse_f32 ? &ps : nullptr));
+    } else {
+        // r -= alpha Ap, r.r; x's update is deferred into the p update
+        const PeerSum ps = c->fuse_combine ? peer_sum(c, s, pl, pg) : PeerSum{};
+        HIPT(update_r_f64(s.nloc, f64(s.r), f64(s.Ap), slot_f64(s, rk), slot_f64(s, pg), slot_f64(s, ro), s.ws,
+                          s.stream, gate_of(s, gated), ts_of(c, s, TK_UR), c->fuse_combine ? &ps : nullptr));
     }
     return CGX_OK;
 }
 
+// ... and after the r.r combine (fold_rr: after its barrier, the kernel sums
+// the partials): p = r + (beta/rsold) p  (serialConjugate.c:239-243), in fp64
+// after the x += alpha p deferred from the r update.  Only a deciding kernel
+// (XP_DECIDE) gets the stop arguments; XP_X_ONLY passes no r.r, so the kernel
+// leaves p alone (F32_REF: nothing to launch, x is current).
+int launch_update_xp(const cgx_ctx *c, const Shard &s, int64_t k, XpForm form, double eps, bool fold_rr) {
+    const int pg = S_PAP + ring(k), rk = S_RR + ring(k);
+    const int rg = S_RR + ring(k + 1), rl = S_LRR + ring(k + 1);
+    const bool decide = form == XP_DECIDE;
+    const double stop_eps = decide ? eps : -1.0;
+    const int64_t stop_k = decide ? k : 0;
+    int64_t *kdone = decide ? slot_i64(s, S_KDONE) : nullptr;
+    double *rrfinal = decide ? slot_f64(s, S_RRFINAL) : nullptr;
+    if (f32ref(c)) {
+        if (form == XP_X_ONLY) return CGX_OK;
+        const PeerSumF32 ps = fold_rr ? peer_sum_f32(c, s, rl, rg) : PeerSumF32{};
+        HIPT(update_p_ref_f32(s.nloc, f32(s.pown), f32(s.r), slot_f32(s, rg), slot_f32(s, rk), s.stream, stop_eps,
+                              stop_k, kdone, rrfinal, rec_of(c, s, decide), fold_rr ? &ps : nullptr));
+    } else {
+        const PeerSum ps = fold_rr ? peer_sum(c, s, rl, rg) : PeerSum{};
+        HIPT(update_xp_f64(s.nloc, f64(s.x), f64(s.pown), f64(s.r), slot_f64(s, rk), slot_f64(s, pg),
+                           form == XP_X_ONLY ? nullptr : slot_f64(s, rg), s.stream, stop_eps, stop_k, kdone, rrfinal,
+                           rec_of(c, s, decide), ts_of(c, s, TK_UXP), fold_rr ? &ps : nullptr));
+    }
+    return CGX_OK;
+}
+
+// One loop iteration k (serialConjugate.c:215-244 / parallel_cg.c:290-323).
+// Returns 1 in *stop when sqrt(r.r) < eps ended the loop (before the p update,
+// as the reference breaks at :235-238).
+// gated: fp64 device-side convergence (the host does not read r.r here; the
+// update kernel decides sqrt(r.r) < eps and later kernels skip themselves).
 int do_iteration(cgx_ctx *c, double eps, int *stop, bool gated) {
     if (c->fused) return do_iteration_poisson(c, eps, stop, gated);
-    if (c->fold_p) return do_iteration_fold_p(c, eps, stop, gated);
-    if (c->fused_p) return do_iteration_fused_p(c, eps, stop, gated);
-    if (c->ref_fused) return do_iteration_ref_fused(c, eps, stop, gated);
+    if (c->fold_p || c->fused_p || c->ref_fused) return do_iteration_two_launch(c, eps, stop, gated);
     const int64_t k = c->k;
     *stop = 0;
     const int pg = S_PAP + ring(k), pl = S_LPAP + ring(k);
@@ -550,100 +534,28 @@ int do_iteration(cgx_ctx *c, double eps, int *stop, bool gated) {
     const bool fold = c->fuse_combine || c->fuse_f32;
     if (fold) TRY(local_barrier(c));
     else TRY(exchange_scalar(c, pl, pg));
+    for (auto &s : c->sh) {
+        TRY(set_dev(s));
+        TRY(launch_update_r(c, s, k, gated));
+    }
     const int rg = S_RR + ring(k + 1), rl = S_LRR + ring(k + 1);
-    const int ro = out_slot(c, rl, rg);
     // the r.r combine folds into k_update_xp_f64 (F32_REF: k_update_p_ref_f32)
     // unless the host reads r.r first (host-checked convergence)
     const bool fuse_rr = fold && (gated || eps < 0.0);
-    for (auto &s : c->sh) {
-        TRY(set_dev(s));
-        if (f32ref(c)) {
-            // x += alpha p; r -= alpha Ap; r.r in one launch  (serialConjugate.c:219-234)
-            const PeerSumF32 ps = c->fuse_f32 ? peer_sum_f32(c, s, pl, pg) : PeerSumF32{};
-            HIPT(update_xr_dot_ref_f32(s.nloc, reinterpret_cast<float *>(s.x), reinterpret_cast<float *>(s.r),
-                                       reinterpret_cast<const float *>(s.pown), reinterpret_cast<const float *>(s.Ap),
-                                       reinterpret_cast<const float *>(slot(s, S_RR + ring(k))),
-                                       reinterpret_cast<const float *>(slot(s, pg)),
-                                       reinterpret_cast<float *>(slot(s, ro)), s.stream, gate_of(s, gated),
-                                       c->fuse_f32 ? &ps : nullptr));
-        } else {
-            // r -= alpha Ap, r.r; x's update is deferred into the p update
-            const PeerSum ps = c->fuse_combine ? peer_sum(c, s, pl, pg) : PeerSum{};
-            HIPT(update_r_f64(s.nloc, reinterpret_cast<double *>(s.r), reinterpret_cast<const double *>(s.Ap),
-                              reinterpret_cast<const double *>(slot(s, S_RR + ring(k))),
-                              reinterpret_cast<const double *>(slot(s, pg)), reinterpret_cast<double *>(slot(s, ro)),
-                              s.ws, s.stream, gate_of(s, gated), ts_of(c, s, TK_UR), c->fuse_combine ? &ps : nullptr));
-        }
-    }
     if (fuse_rr) TRY(local_barrier(c));  // MPI_Allreduce(r.r)  parallel_cg.c:313, summed by k_update_xp_f64
     else TRY(exchange_scalar(c, rl, rg));
     c->k = k + 1;
     c->total_iters += 1;
-    if (gated) {  // x (+ p unless converged) on the device, stopping rule decided there
+    if (!gated) TRY(host_check_stop(c, rg, eps, stop));
+    // gated: x (+ p unless converged) on the device, stopping rule decided
+    // there; a stop the host saw: the deferred x += alpha p, without the p
+    // update (F32_REF: x is current, nothing more to enqueue)
+    const XpForm form = gated ? XP_DECIDE : *stop ? XP_X_ONLY : XP_UPDATE;
+    if (!(form == XP_X_ONLY && f32ref(c)))
         for (auto &s : c->sh) {
             TRY(set_dev(s));
-            if (f32ref(c)) {  // x is current; the p update decides the stop first
-                const PeerSumF32 ps = fuse_rr ? peer_sum_f32(c, s, rl, rg) : PeerSumF32{};
-                HIPT(update_p_ref_f32(s.nloc, reinterpret_cast<float *>(s.pown), reinterpret_cast<const float *>(s.r),
-                                      reinterpret_cast<const float *>(slot(s, rg)),
-                                      reinterpret_cast<const float *>(slot(s, S_RR + ring(k))), s.stream, eps, k,
-                                      reinterpret_cast<int64_t *>(slot(s, S_KDONE)),
-                                      reinterpret_cast<double *>(slot(s, S_RRFINAL)), rec_of(c, s, gated),
-                                      fuse_rr ? &ps : nullptr));
-                continue;
-            }
-            const PeerSum ps = fuse_rr ? peer_sum(c, s, rl, rg) : PeerSum{};
-            HIPT(update_xp_f64(s.nloc, reinterpret_cast<double *>(s.x), reinterpret_cast<double *>(s.pown),
-                               reinterpret_cast<const double *>(s.r),
-                               reinterpret_cast<const double *>(slot(s, S_RR + ring(k))),
-                               reinterpret_cast<const double *>(slot(s, pg)),
-                               reinterpret_cast<const double *>(slot(s, rg)), s.stream, eps, k,
-                               reinterpret_cast<int64_t *>(slot(s, S_KDONE)),
-                               reinterpret_cast<double *>(slot(s, S_RRFINAL)), rec_of(c, s, gated),
-                               ts_of(c, s, TK_UXP), fuse_rr ? &ps : nullptr));
+            TRY(launch_update_xp(c, s, k, form, eps, fuse_rr));
         }
-        phase_iter_end(c);
-        return CGX_OK;
-    }
-    if (eps >= 0.0) {  // if (sqrt(beta) < EPSILON) break;  serialConjugate.c:235-238
-        double rr = 0.0;
-        TRY(read_scalar(c, rg, &rr));
-        c->last_rr = rr;
-        if (std::sqrt(rr) < eps) {
-            c->converged = 1;
-            c->state = ST_CONVERGED;
-            *stop = 1;
-            if (!f32ref(c))  // the deferred x += alpha p, without the p update
-                for (auto &s : c->sh) {
-                    TRY(set_dev(s));
-                    HIPT(update_xp_f64(s.nloc, reinterpret_cast<double *>(s.x), reinterpret_cast<double *>(s.pown),
-                                       reinterpret_cast<const double *>(s.r),
-                                       reinterpret_cast<const double *>(slot(s, S_RR + ring(k))),
-                                       reinterpret_cast<const double *>(slot(s, pg)), nullptr, s.stream, -1.0, 0,
-                                       nullptr, nullptr, nullptr, ts_of(c, s, TK_UXP)));
-                }
-            phase_iter_end(c);
-            return CGX_OK;
-        }
-    }
-    for (auto &s : c->sh) {  // p = r + (beta/rsold) p    serialConjugate.c:239-243
-        TRY(set_dev(s));
-        if (f32ref(c)) {
-            const PeerSumF32 ps = fuse_rr ? peer_sum_f32(c, s, rl, rg) : PeerSumF32{};
-            HIPT(update_p_ref_f32(s.nloc, reinterpret_cast<float *>(s.pown),
-                                  reinterpret_cast<const float *>(s.r), reinterpret_cast<const float *>(slot(s, rg)),
-                                  reinterpret_cast<const float *>(slot(s, S_RR + ring(k))), s.stream, -1.0, 0,
-                                  nullptr, nullptr, nullptr, fuse_rr ? &ps : nullptr));
-        } else {  // x += alpha p (deferred from the r update), then p = r + beta p
-            const PeerSum ps = fuse_rr ? peer_sum(c, s, rl, rg) : PeerSum{};
-            HIPT(update_xp_f64(s.nloc, reinterpret_cast<double *>(s.x), reinterpret_cast<double *>(s.pown),
-                               reinterpret_cast<const double *>(s.r),
-                               reinterpret_cast<const double *>(slot(s, S_RR + ring(k))),
-                               reinterpret_cast<const double *>(slot(s, pg)),
-                               reinterpret_cast<const double *>(slot(s, rg)), s.stream, -1.0, 0, nullptr, nullptr,
-                               nullptr, ts_of(c, s, TK_UXP), fuse_rr ? &ps : nullptr));
-        }
-    }
     phase_iter_end(c);
     return CGX_OK;
 }
@@ -653,12 +565,15 @@ int do_iteration(cgx_ctx *c, double eps, int *stop, bool gated) {
 // process's first solve: 9-14 us against 6-7 us per hipLaunchKernel), about
 // 20 us over a small system's first solve -- the only solve `cg_hip` runs.
 // One GPU, small n: the context pays it at creation.  The solve's start runs
-// for real on alloc_shard's zeroed x and b (A x with x = 0, whatever A holds:
-// only r, p, Ap and the scalar slots are written), then two gated iterations
-// whose kernels all return at once (the record holds -1: converged before
-// any iteration, under both gate tests) and one record of each lookahead
-// event; the written buffers and the host
-// state then go back to what alloc_shard left.  CGX_WARM=0: no warm-up.
+// for real on alloc_shard's zeroed x and b (A x with x = 0, whatever A holds),
+// then two gated iterations whose kernels all return at once (the record
+// holds -1: converged before any iteration, under both gate tests) and one
+// record of each lookahead event; the written buffers and the host state then
+// go back to what alloc_shard left.  CGX_WARM=0: no warm-up.
+// What that can write on an eligible context -- one GPU, dense, A resident
+// and not symmetric (no tile buffers, no symv partials), no timing events, no
+// phase stamps -- and so what warm_solve_kernels clears: r, Ap, pfull, p_alt
+// (the folded form's) and the scalar slots.
 constexpr int64_t kWarmMaxN = 16384;
 bool warm_eligible(const cgx_ctx *c) {
     if (c->mode != M_SINGLE || c->op != OP_DENSE || c->n > kWarmMaxN) return false;
@@ -684,13 +599,12 @@ int warm_solve_kernels(cgx_ctx *c) {
     if (s.p_alt) HIPT(hipMemsetAsync(s.p_alt, 0, c->lda * es, s.stream));
     HIPT(hipMemsetAsync(s.scal, 0, kScalSlots * 8, s.stream));
     HIPT(hipStreamSynchronize(s.stream));
+    reset_solve_state(c, ST_IDLE);
+    // ... and what outlives a solve, or only a later cgx_iterate call sets
     s.x_zero = true;
-    s.h_rec[0] = s.h_rec[1] = 0;
-    c->state = ST_IDLE;
-    c->k = c->xd_k0 = c->total_iters = 0;
-    c->converged = 0;
+    c->xd_k0 = c->total_iters = 0;
     c->last_rr = 0.0;
-    c->rr_unsummed = c->x_incomplete = c->x_deferred = c->xalpha_pending = c->iter_failed = false;
+    c->rr_unsummed = false;
     return CGX_OK;
 }
 

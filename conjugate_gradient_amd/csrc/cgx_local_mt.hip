@@ -82,55 +82,37 @@ static int shard_iteration(LocalPool &P, Shard &d) {
     const int64_t k = P.k;
     const bool gated = P.gated;
     const int S = (int)c->sh.size();
-    const int pg = S_PAP + ring(k), pl = S_LPAP + ring(k);
-    const int rg = S_RR + ring(k + 1), rl = S_LRR + ring(k + 1);
+    const int pl = S_LPAP + ring(k);
     const size_t es = (size_t)c->es;
-    auto D = [](void *q) { return reinterpret_cast<double *>(q); };
-    auto CD = [](const void *q) { return reinterpret_cast<const double *>(q); };
     TRY(set_dev(d));
     // 1. p_k is in place (the previous x/p update): everyone may read it
     HIPT(hipEventRecord(d.ev_pready, d.stream));
     BAR();
     const PeerTable pown = peer_table(c, &Shard::pown, 0);
-    const bool timing = (c->flags & CGX_TIMING) && d.index == 0;
     if (c->overlap) {  // parallel_cg.c:290-293, overlapped (overlapped_matvec)
         for (auto &s : c->sh) HIPT(hipStreamWaitEvent(d.cstream, s.ev_pready, 0));
         HIPT(gather_slices(pown, S, d.index, d.nloc * (int64_t)es, d.pfull, d.cstream));
         TRY(overlap_matvecs(c, d, pl, gated));
     } else {  // MPI_Allgather(local_p -> p), then the matVec (parallel_cg.c:290-293)
-        if (timing && d.ev_used >= kEvPairs) TRY(timing_resolve(c));
-        if (timing) HIPT(hipEventRecord(d.ev_t[2 * d.ev_used], d.stream));
+        TRY(timing_begin(c, d));
         for (auto &s : c->sh)
             if (&s != &d) HIPT(hipStreamWaitEvent(d.stream, s.ev_pready, 0));
         HIPT(gather_slices(pown, S, d.index, d.nloc * (int64_t)es, d.pfull, d.stream));
         TRY(matvec_rows(c, d, d.plan, d.A, 0, d.nloc, d.pfull, true, pl, gated, ts_of(c, d, TK_MV)));
-        if (timing) {
-            HIPT(hipEventRecord(d.ev_t[2 * d.ev_used + 1], d.stream));
-            d.ev_used++;
-        }
+        TRY(timing_end(c, d));
     }
     // 2. MPI_Allreduce(p.Ap) (parallel_cg.c:294): summed by k_update_r_f64 itself
     HIPT(hipEventRecord(d.ev_sync, d.stream));
     BAR();
     for (auto &s : c->sh)
         if (&s != &d) HIPT(hipStreamWaitEvent(d.stream, s.ev_sync, 0));
-    const PeerSum pap = peer_sum(c, d, pl, pg);
-    HIPT(update_r_f64(d.nloc, D(d.r), CD(d.Ap), CD(slot(d, S_RR + ring(k))), CD(slot(d, pg)), D(slot(d, rl)), d.ws,
-                      d.stream, gate_of(d, gated), ts_of(c, d, TK_UR), &pap));
+    TRY(launch_update_r(c, d, k, gated));
     // 3. MPI_Allreduce(r.r) (parallel_cg.c:313): summed by k_update_xp_f64
     HIPT(hipEventRecord(d.ev_sync2, d.stream));
     BAR();
     for (auto &s : c->sh)
         if (&s != &d) HIPT(hipStreamWaitEvent(d.stream, s.ev_sync2, 0));
-    const PeerSum rr = peer_sum(c, d, rl, rg);
-    if (gated)
-        HIPT(update_xp_f64(d.nloc, D(d.x), D(d.pown), CD(d.r), CD(slot(d, S_RR + ring(k))), CD(slot(d, pg)),
-                           CD(slot(d, rg)), d.stream, P.eps, k, reinterpret_cast<int64_t *>(slot(d, S_KDONE)),
-                           D(slot(d, S_RRFINAL)), rec_of(c, d, gated), ts_of(c, d, TK_UXP), &rr));
-    else
-        HIPT(update_xp_f64(d.nloc, D(d.x), D(d.pown), CD(d.r), CD(slot(d, S_RR + ring(k))), CD(slot(d, pg)),
-                           CD(slot(d, rg)), d.stream, -1.0, 0, nullptr, nullptr, nullptr, ts_of(c, d, TK_UXP), &rr));
-    return CGX_OK;
+    return launch_update_xp(c, d, k, gated ? XP_DECIDE : XP_UPDATE, P.eps, /*fold_rr=*/true);
 }
 
 static void worker(LocalPool *P, int index) {

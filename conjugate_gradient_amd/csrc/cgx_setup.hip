@@ -305,12 +305,12 @@ int alloc_overlap(cgx_ctx *c) {
     return CGX_OK;
 }
 
-// The two-launch dense iteration (do_iteration_fused_p): one GPU, fp64,
+// The two-launch dense iteration (launch_fused_p): one GPU, fp64,
 // resident row-major A, n up to kFusePMax by default (the p update then runs
 // in one block: n doubles read twice and written once by one CU, a few us at
 // n = 8192); CGX_FUSE_P=0 keeps three launches, =1 uses two at any n.
 constexpr int64_t kFusePMax = 8192;
-// ... and the p update is folded into the next matVec (do_iteration_fold_p)
+// ... and the p update is folded into the next matVec (launch_fold_p)
 // up to kFoldPMax with k_matvec_fold_f64 -- measured per iteration
 // (profiles/r03_iteration_floor.jsonl, device clock) 9.6 vs 10.2 us at
 // n = 512, 11.8 vs 12.0 at 1024, 13.9-14.0 vs 14.2 at 2048 -- and wherever
@@ -343,7 +343,7 @@ static bool can_fuse_p(const cgx_ctx *c) {
 // The F32_REF counterparts: with resident row-major A the matVec's last
 // block runs vecVec(p, Ap) over the shard's rows (the shard's partial in
 // row-block modes), and on one GPU the iteration is two launches
-// (do_iteration_ref_fused).  CGX_REF_FUSE=0 keeps the separate launches
+// (launch_ref_fused).  CGX_REF_FUSE=0 keeps the separate launches
 // (matVec, p.Ap, x/r + r.r, p).  The same float operations in the same order
 // either way.
 static bool can_fuse_ref_dot(const cgx_ctx *c) {

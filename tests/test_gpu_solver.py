@@ -732,6 +732,57 @@ def test_f32ref_two_launch_iteration_bitwise_equals_four(monkeypatch, name):
         assert conv and dp == it and np.array_equal(bits(xp), bits(xr)), key
 
 
+@pytest.mark.parametrize("gated", ["1", "0"])
+@pytest.mark.parametrize("form,env", [("three", {"CGX_FUSE_P": "0", "CGX_FOLD_P": "0"}),
+                                      ("two", {"CGX_FUSE_P": "1", "CGX_FOLD_P": "0"}),
+                                      ("fold", {"CGX_FUSE_P": "1", "CGX_FOLD_P": "1"}),
+                                      ("ref_two", {}), ("ref_four", {"CGX_REF_FUSE": "0"})])
+@pytest.mark.parametrize("n", [130, 2048])
+def test_creation_warmup_leaves_no_trace(monkeypatch, n, form, env, gated):
+    """A small one-GPU dense context runs the solve's start and two no-op
+    iterations at creation (the kernels' first launches) and then puts the
+    buffers and the host's solve state back; CGX_WARM=0 leaves it out.  Either
+    way the new context is idle with no iterations counted, and a solve and a
+    fixed-count continuation give the same x bit for bit, the same counts and
+    the same r.r -- in each of the three fp64 and two CGX_F32_REF iteration
+    forms, device-gated and host-checked; n = 130 (one 128-column chunk and a
+    tail, one block) and 2048 (the LDS matVec, the first size with p_alt)."""
+    ref = form.startswith("ref")
+    dtype = np.float32 if ref else np.float64
+    A, b = oracle.spd_hash(n, seed=5)
+    A, b = A.astype(dtype), b.astype(dtype)
+    monkeypatch.delenv("CGX_REF_FUSE", raising=False)
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    monkeypatch.setenv("CGX_GATED", gated)
+    res = {}
+    for warm in (None, "0"):
+        if warm is None:
+            monkeypatch.delenv("CGX_WARM", raising=False)
+        else:
+            monkeypatch.setenv("CGX_WARM", warm)
+        with cg.Solver(n, flags=cg.CGX_F32_REF if ref else 0) as s:
+            st0 = s.stats()
+            assert st0.iterations == 0 and st0.total_iterations == 0, (warm, st0.iterations, st0.total_iterations)
+            with pytest.raises(cg.CgxError) as ei:
+                s.iterate(1)
+            assert ei.value.code == -6  # CGX_ERR_STATE: still idle
+            # the context runs the form the case names (two launches: fp64 "two" / "fold", F32_REF "ref_two")
+            assert bool(s.info.flags & cg.CGX_FUSED_ACTIVE) == (form in ("two", "fold", "ref_two"))
+            assert bool(s.info.flags & cg.CGX_FOLD_ACTIVE) == (form == "fold")
+            s.set_system(A, b)
+            x1, _ = s.solve(None, eps=1e-10)
+            st1 = s.stats()
+            s.begin()
+            s.iterate(7)
+            x2 = s.get_x()
+            st2 = s.stats()
+        res[warm] = (x1, x2, [(st.iterations, st.total_iterations, st.converged, st.rr) for st in (st1, st2)])
+    assert np.array_equal(res[None][0], res["0"][0])
+    assert np.array_equal(res[None][1], res["0"][1])
+    assert res[None][2] == res["0"][2]
+
+
 def test_errors_are_reported():
     with cg.Solver(8) as s:
         with pytest.raises(cg.CgxError) as ei:
