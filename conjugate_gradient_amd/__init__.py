@@ -31,7 +31,7 @@ import subprocess
 import numpy as np
 
 __all__ = [
-    "CGX_F64", "CGX_F32_REF", "CGX_TIMING", "CGX_HOST_STREAM", "CGX_NO_OVERLAP", "CGX_COMM_P2P", "CGX_SYMMETRIC",
+    "CGX_F64", "CGX_F32_REF", "CGX_A_F32", "CGX_TIMING", "CGX_HOST_STREAM", "CGX_NO_OVERLAP", "CGX_COMM_P2P", "CGX_SYMMETRIC",
     "CGX_PHASES", "CGX_PEER_ACTIVE", "CGX_SMALL_ACTIVE", "CGX_FOLD_ACTIVE", "CGX_XDEFER_ACTIVE", "CGX_XDEFER3_ACTIVE",
     "CGX_PULL_ACTIVE", "CGX_FOLDED_ACTIVE", "CGX_HALO_PULL_ACTIVE", "CGX_THREADS_ACTIVE", "CGX_HALO_OVERLAP_ACTIVE",
     "PHASE_NAMES", "overlap_rule", "CgxError", "Stats",
@@ -43,6 +43,7 @@ __all__ = [
 
 CGX_F64 = 0x0
 CGX_F32_REF = 0x1
+CGX_A_F32 = 0x2
 CGX_TIMING = 0x100
 CGX_HOST_STREAM = 0x200
 CGX_NO_OVERLAP = 0x400
@@ -225,6 +226,11 @@ def _dtype(flags: int) -> np.dtype:
     return np.dtype(np.float32) if flags & CGX_F32_REF else np.dtype(np.float64)
 
 
+def _a_dtype(flags: int) -> np.dtype:
+    """A's element type: float32 under CGX_A_F32 (beside float64 vectors), else the vectors'."""
+    return np.dtype(np.float32) if flags & CGX_A_F32 else _dtype(flags)
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     _check(lib().cgx_device_count(ctypes.byref(n)), "cgx_device_count")
@@ -343,14 +349,22 @@ def _fits(arrs, n: int, what: str) -> None:
 
 
 def matVec(A: DeviceArray, v: DeviceArray, out: DeviceArray, rows: int, cols: int, lda: int | None = None) -> None:
-    """serialConjugate.c:109-120 / parallel_cg.c:172-184 (rows = local_row)."""
+    """serialConjugate.c:109-120 / parallel_cg.c:172-184 (rows = local_row).
+    A float32 ``A`` with float64 ``v`` and ``out`` runs the CGX_A_F32 kernel
+    (A widened exactly, fp64 arithmetic)."""
     lda = lda or cols
     _need(rows >= 0 and cols >= 0 and lda >= cols, "matVec: need rows, cols >= 0 and lda >= cols")
     if rows and cols:
         _fits([A], (rows - 1) * lda + cols, "matVec A")
         _fits([v], cols, "matVec v")
         _fits([out], rows, "matVec out")
-    _check(lib().cgx_matvec(_dt_flag(A.dtype), A.ptr, lda or cols, rows, cols, v.ptr, out.ptr, None), "cgx_matvec")
+    dt = _dt_flag(A.dtype)
+    if A.dtype == np.float32 and v.dtype == np.float64 and out.dtype == np.float64:
+        dt = CGX_A_F32
+    else:
+        _need(v.dtype == A.dtype and out.dtype == A.dtype,
+              "matVec: A, v and out of one dtype, or a float32 A with float64 v and out")
+    _check(lib().cgx_matvec(dt, A.ptr, lda or cols, rows, cols, v.ptr, out.ptr, None), "cgx_matvec")
 
 
 def vecVec(a: DeviceArray, b: DeviceArray, out: DeviceArray, n: int | None = None) -> None:
@@ -393,7 +407,12 @@ def update_p(p, r, rr, rsold, n=None) -> None:
 # ----------------------------------------------------------------------------
 class Solver:
     """A CG context: one GPU, several row-block shards in this process, or one
-    rank of a one-process-per-GPU job (RCCL)."""
+    rank of a one-process-per-GPU job (RCCL).
+
+    Arrays handed in are cast silently (``np.ascontiguousarray``) to the
+    context's types: float32 under CGX_F32_REF, float64 otherwise; under
+    CGX_A_F32 A is cast to float32 (a float64 A is rounded to nearest) while
+    b and x are cast to float64."""
 
     def __init__(self, n: int, *, flags: int = CGX_F64, device: int = 0, devices=None,
                  rank: int | None = None, nranks: int | None = None, unique_id: bytes | None = None,
@@ -467,7 +486,7 @@ class Solver:
 
     # data
     def set_system(self, A: np.ndarray, b: np.ndarray, x0: np.ndarray | None = None) -> None:
-        A = np.ascontiguousarray(A, self.dtype)
+        A = np.ascontiguousarray(A, _a_dtype(self.flags))
         b = np.ascontiguousarray(b, self.dtype)
         x0 = np.zeros(self.n, self.dtype) if x0 is None else np.ascontiguousarray(x0, self.dtype)
         _need(A.shape == (self.n, self.n), f"set_system: A has shape {A.shape}, ({self.n}, {self.n}) needed")
@@ -476,7 +495,8 @@ class Solver:
         _check(lib().cgx_set_system(self._h, _ptr(A), _ptr(b), _ptr(x0)), "cgx_set_system")
 
     def set_rows(self, row0: int, A_rows=None, b_rows=None, x_rows=None) -> None:
-        arrs = [None if a is None else np.ascontiguousarray(a, self.dtype) for a in (A_rows, b_rows, x_rows)]
+        arrs = [None if a is None else np.ascontiguousarray(a, dt)
+                for a, dt in zip((A_rows, b_rows, x_rows), (_a_dtype(self.flags), self.dtype, self.dtype))]
         _need(any(a is not None for a in arrs), "set_rows: nothing to set")
         nrows = next(a.shape[0] for a in arrs if a is not None)
         if arrs[0] is not None:
@@ -593,9 +613,12 @@ def conjugrad(A: np.ndarray, b: np.ndarray, x: np.ndarray, *, eps: float = 1e-6,
     parallel_cg.c's row-block split with P = len(shards) (parallel_cg.c:248).
     The dtype of ``x`` picks the arithmetic unless ``flags`` is given:
     float32 -> CGX_F32_REF (the reference's float results bit for bit),
-    float64 -> CGX_F64."""
+    float64 -> CGX_F64, or CGX_A_F32 when ``A`` is float32 (A stays float on
+    the GPU, fp64 arithmetic)."""
     if flags is None:
         flags = CGX_F32_REF if x.dtype == np.float32 else CGX_F64
+        if x.dtype == np.float64 and getattr(A, "dtype", None) == np.float32 and shards is None:
+            flags = CGX_A_F32
     n = b.shape[0]
     with Solver(n, flags=flags, devices=shards) as s:
         s.set_system(A, b, x)

@@ -29,7 +29,9 @@
  * parsing), --spd N [--seed S] (on-device synthetic system instead of files),
  * --symmetric (fp64, one GPU: keep only A's upper-triangle tiles, half the
  * bytes per matVec; CG's A is symmetric by contract, the lower triangle
- * outside the diagonal tiles is not read).
+ * outside the diagonal tiles is not read), --a-fp32 (one GPU: A parsed and
+ * kept on the GPU as float, exactly what initialize() reads, with b, x0 and
+ * all arithmetic in fp64 -- CGX_A_F32, half the bytes per matVec).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -107,9 +109,9 @@ static double now_s(void) {
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "usage: %s [--gpus P [--p2p]] [--fp32-ref | --symmetric] [--eps E] [--max-iter M] [--dims FILE] [--n N]\n"
+            "usage: %s [--gpus P [--p2p]] [--fp32-ref | --symmetric | --a-fp32] [--eps E] [--max-iter M] [--dims FILE] [--n N]\n"
             "          [--threads T] [--print-x] [--stats] matrixA vectorb initialguess\n"
-            "       %s --spd N [--seed S] [--gpus P] [--eps E] [--max-iter M] [--stats]\n",
+            "       %s --spd N [--seed S] [--gpus P] [--a-fp32] [--eps E] [--max-iter M] [--stats]\n",
             prog, prog);
 }
 
@@ -261,7 +263,7 @@ static int opt_double(const char *name, const char *v, double *out) {
 
 int main(int argc, char **argv) {
     const double t_prog0 = now_s();
-    int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0;
+    int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0, a_fp32 = 0;
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
@@ -280,6 +282,7 @@ int main(int argc, char **argv) {
             gpus = (v < 0 || v > 1000) ? -1 : (int)v;
         } else if (!strcmp(a, "--fp32-ref")) fp32ref = 1;
         else if (!strcmp(a, "--symmetric")) symmetric = 1;
+        else if (!strcmp(a, "--a-fp32")) a_fp32 = 1;
         else if (!strcmp(a, "--p2p")) p2p = 1;
         else if (!strcmp(a, "--eps") && has_val) {
             if (!opt_double(a, argv[++i], &eps)) return 2;
@@ -318,6 +321,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--symmetric is fp64 on one GPU (no --fp32-ref, --gpus 1)\n");
         return 2;
     }
+    if (a_fp32 && (fp32ref || symmetric || gpus != 1)) {
+        fprintf(stderr, "--a-fp32 is float A with fp64 arithmetic on one GPU (no --fp32-ref, no --symmetric, --gpus 1)\n");
+        return 2;
+    }
 
     /* ---- N ---------------------------------------------------------------- */
     int64_t n = 0;
@@ -339,8 +346,11 @@ int main(int argc, char **argv) {
     printf("Computing cg of matrix size : %lld\n", (long long)n * (long long)n); /* serialConjugate.c:58 */
     fflush(stdout);
 
-    const int flags = (fp32ref ? CGX_F32_REF : (CGX_F64 | (symmetric ? CGX_SYMMETRIC : 0))) | (p2p ? CGX_COMM_P2P : 0);
-    const size_t es = fp32ref ? 4 : 8;
+    const int flags = (fp32ref ? CGX_F32_REF : (CGX_F64 | (symmetric ? CGX_SYMMETRIC : 0))) | (p2p ? CGX_COMM_P2P : 0) |
+                      (a_fp32 ? CGX_A_F32 : 0);
+    const size_t es = fp32ref ? 4 : 8;           /* b, x */
+    const size_t aes = a_fp32 ? 4 : es;          /* A: float with --a-fp32, as initialize() reads it */
+    const int a_as_float = fp32ref || a_fp32;
     void *x = malloc((size_t)n * es);
     void *A = NULL, *b = NULL;
     /* static: the release thread may still read it while an error path
@@ -373,7 +383,7 @@ int main(int argc, char **argv) {
         if (!b) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     } else {
         /* initialize(A), initialize(b), initialize(x0): serialConjugate.c:65-67 */
-        if (big_alloc(&Abuf, (size_t)n * (size_t)n * es) != 0) A = NULL;
+        if (big_alloc(&Abuf, (size_t)n * (size_t)n * aes) != 0) A = NULL;
         else A = Abuf.p;
         b = malloc((size_t)n * es);
         if (!A || !b) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
@@ -404,10 +414,10 @@ int main(int argc, char **argv) {
         if (!read_rc) {
             const char *rm = getenv("CGX_CLI_RING_MB"), *bm = getenv("CGX_CLI_BLOCK_MB");
             const double ring_mb = (rm && atof(rm) > 0) ? atof(rm) : 1024.0;
-            const size_t row_bytes = (size_t)n * es;
+            const size_t row_bytes = (size_t)n * aes;
             const size_t block_bytes = (size_t)(((bm && atof(bm) > 0) ? atof(bm) : 128.0) * 1048576.0);
             st.n = n;
-            st.es = es;
+            st.es = aes;
             st.block_rows = (int64_t)(block_bytes / row_bytes) > 0 ? (int64_t)(block_bytes / row_bytes) : 1;
             if (st.block_rows > n) st.block_rows = n;
             st.nblocks = (n + st.block_rows - 1) / st.block_rows;
@@ -415,7 +425,7 @@ int main(int argc, char **argv) {
             if (slots < 2) slots = 2;
             if (slots > st.nblocks) slots = st.nblocks;
             st.nslots = (int)slots;
-            st.as_float = fp32ref;
+            st.as_float = a_as_float;
             st.threads = threads;
             st.slot_bytes = (size_t)st.block_rows * row_bytes;
             st.filled = calloc((size_t)st.nslots, sizeof(int));
@@ -458,7 +468,7 @@ int main(int argc, char **argv) {
         }
     } else {
         read_rc = spd_n > 0 ? 0
-                            : (read_file(pos[0], n * n, fp32ref, A, threads) ||
+                            : (read_file(pos[0], n * n, a_as_float, A, threads) ||
                                read_file(pos[1], n, fp32ref, b, threads) || read_file(pos[2], n, fp32ref, x, 1));
         t_parsed = now_s();
         if (threaded) pthread_join(creator, NULL);  /* before any exit: HIP may be starting up on it */

@@ -54,8 +54,11 @@ int dev_ws(RedWs *out) {
     return CGX_OK;
 }
 
-int check_dtype(int dtype) {
-    if (dtype != CGX_F64 && dtype != CGX_F32_REF) return fail(CGX_ERR_ARG, "dtype must be CGX_F64 or CGX_F32_REF");
+int check_dtype(int dtype, bool matvec) {
+    if (matvec && dtype == CGX_A_F32) return CGX_OK;
+    if (dtype != CGX_F64 && dtype != CGX_F32_REF)
+        return fail(CGX_ERR_ARG, matvec ? "dtype must be CGX_F64, CGX_F32_REF or CGX_A_F32"
+                                        : "dtype must be CGX_F64 or CGX_F32_REF");
     return CGX_OK;
 }
 
@@ -144,7 +147,7 @@ int cgx_dev_synchronize(void) {
 
 int cgx_matvec(int dtype, const void *A, int64_t lda, int64_t rows, int64_t cols, const void *v, void *out,
                void *stream) {
-    TRY(check_dtype(dtype));
+    TRY(check_dtype(dtype, /*matvec=*/true));
     if (rows < 0 || cols < 0 || lda < cols) return fail(CGX_ERR_SHAPE, "bad matVec shape");
     if (!A || !v || !out) return fail(CGX_ERR_ARG, "NULL pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -157,6 +160,11 @@ int cgx_matvec(int dtype, const void *A, int64_t lda, int64_t rows, int64_t cols
     HIPT(hipGetDevice(&dev));
     RedWs ws;
     TRY(dev_ws(&ws));
+    if (dtype == CGX_A_F32) {  // float A, double v and out
+        HIPT(matvec_a32(plan_matvec_a32(dev, rows, 0, 0, -1, 0, cols), static_cast<const float *>(A), lda, rows, cols,
+                        static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws, s));
+        return CGX_OK;
+    }
     MatvecPlan pl = plan_matvec_f64(dev, rows, 0, 0, -1, 0, cols);
     const char *sm = std::getenv("CGX_MV_SMALL");
     if (cols == lda && sm && *sm == '2') {  // the solver's LDS-staged kernel here too (tests)

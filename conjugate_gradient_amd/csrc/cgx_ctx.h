@@ -255,6 +255,7 @@ struct cgx_ctx {
     int nranks = 1;
     int flags = 0;
     int es = 8;
+    int aes = 8;  // A's element size: es, or 4 with CGX_A_F32 (float A beside double vectors)
     Mode mode = M_SINGLE;
     std::vector<Shard> sh;
     State state = ST_IDLE;
@@ -350,6 +351,7 @@ struct cgx_ctx {
 namespace cgxh {
 
 inline bool f32ref(const cgx_ctx *c) { return (c->flags & CGX_F32_REF) != 0; }
+inline bool a32(const cgx_ctx *c) { return (c->flags & CGX_A_F32) != 0; }
 inline void *slot(const Shard &s, int i) { return s.scal + 8 * i; }
 inline bool p2p(const cgx_ctx *c) { return (c->flags & CGX_COMM_P2P) != 0; }
 // Where a kernel writes its (partial) scalar: the global slot directly when
@@ -458,6 +460,6 @@ bool warm_eligible(const cgx_ctx *c);
 int warm_solve_kernels(cgx_ctx *c);
 // cgx_api.hip
 int dev_ws(RedWs *out);
-int check_dtype(int dtype);
+int check_dtype(int dtype, bool matvec = false);  // matvec: CGX_A_F32 is a dtype too
 
 }  // namespace cgxh

@@ -14,6 +14,10 @@ int matvec_rows(cgx_ctx *c, Shard &s, const MatvecPlan &pl, const char *Arows, i
                 const char *vec, bool fuse_dot, int dot_slot, bool gated, int64_t *ts) {
     if (f32ref(c)) {
         HIPT(matvec_ref_f32(f32(Arows), c->lda, rows, c->n, f32(vec), f32(s.Ap) + r0, s.stream, gate_of(s, gated)));
+    } else if (a32(c)) {  // float A, fp64 everything else; every column to lda like the fp64 path
+        HIPT(matvec_a32(pl, f32(Arows), c->lda, rows, c->lda, f64(vec), f64(s.Ap) + r0,
+                        fuse_dot ? f64(s.pown) + r0 : nullptr, fuse_dot ? slot_f64(s, dot_slot) : nullptr, s.ws,
+                        s.stream, gate_of(s, gated), ts));
     } else if (c->rot && Arows == s.A && r0 == 0 && rows == s.nloc) {
         // the block's own columns, then the rest, summed apart and added: the
         // overlapped form's bits in one launch (cgx_ctx::rot)
@@ -830,6 +834,17 @@ int cgx_set_matvec_plan(cgx_ctx *c, int rows_per_wave, int chunks_in_flight, int
     if (f32ref(c) || c->op != OP_DENSE || (c->flags & CGX_SYMMETRIC))
         return fail(CGX_ERR_ARG, "only the fp64 row-major dense matVec has a tunable plan");
     const int R = rows_per_wave, U = chunks_in_flight;
+    if (a32(c)) {
+        if (!matvec_a32_plan_ok(R, U, nontemporal))
+            return fail(CGX_ERR_ARG, "CGX_A_F32: (rows_per_wave, chunks_in_flight) must be one of (1,4) (1,8) (2,4) "
+                                     "(4,2) (4,4) (8,2) and the load policy 2 or 8 (got %d, %d, %d)", R, U,
+                        nontemporal);
+        for (auto &s : c->sh) {
+            TRY(set_dev(s));
+            s.plan = plan_matvec_a32(s.dev, s.nloc, R, U, nontemporal, blocks_per_cu, c->lda);
+        }
+        return CGX_OK;
+    }
     if (R != 1 && R != 2 && R != 4 && R != 8) return fail(CGX_ERR_ARG, "rows_per_wave must be 1, 2, 4 or 8");
     if (U != 2 && U != 4 && U != 8) return fail(CGX_ERR_ARG, "chunks_in_flight must be 2, 4 or 8");
     if (nontemporal != 0 && nontemporal != 1 && nontemporal != 2 && nontemporal != 8)

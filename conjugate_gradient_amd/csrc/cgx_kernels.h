@@ -72,6 +72,7 @@ struct MatvecPlan {
     int nt = 1;       // non-temporal loads of A
     int blocks = 0;   // grid (256-thread blocks), grid-stride over row groups
     int small = 0;    // > 0: k_matvec_small_f64 with this many threads per block (vector in LDS)
+    int a32 = 0;      // 1: k_matvec_a32's plan (float A; U counts 256-column chunks, nt is 2 or 8)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -106,6 +107,17 @@ hipError_t matvec_f64_cols(const MatvecPlan &pl, const double *A, int64_t lda, i
                            int64_t col_first, int64_t col_count, bool accumulate, const double *v, double *out,
                            const double *pown, double *dot_out, const RedWs &ws, hipStream_t s,
                            const int64_t *gate = nullptr, int64_t *ts = nullptr, int64_t col_seg = 0);
+// CGX_A_F32 (cgx_matvec_a32.hip): A stored as float, widened exactly, fp64
+// FMAs; v, out, pown and the fused dot are double as above.  The plan comes
+// from plan_matvec_a32: R/U/nt <= 0 / < 0 pick the defaults (env
+// CGX_MV_A32_PLAN="R=..,U=..,nt=..,bpc=.." may override with an instantiated
+// plan); matvec_a32_plan_ok says whether (R, U, nt) is instantiated.
+bool matvec_a32_plan_ok(int R, int U, int nt);
+MatvecPlan plan_matvec_a32(int device, int64_t rows, int R = 0, int U = 0, int nt = -1, int blocks_per_cu = 0,
+                           int64_t cols = 0);
+hipError_t matvec_a32(const MatvecPlan &pl, const float *A, int64_t lda, int64_t rows, int64_t cols, const double *v,
+                      double *out, const double *pown, double *dot_out, const RedWs &ws, hipStream_t s,
+                      const int64_t *gate = nullptr, int64_t *ts = nullptr);
 // r = b - Ax; p = r (if p); *rr_out = r.r (if rr_out).  Ax == nullptr: Ax = 0
 // (r = b - 0.0).  clear2: two int64 the kernel zeroes (the convergence record).
 hipError_t residual_f64(int64_t n, const double *b, const double *Ax, double *r, double *p,
@@ -154,6 +166,9 @@ hipError_t dot_f64(int64_t n, const double *a, const double *b, double *out,
 // Rows [row0, row0+nrows) of the counter-hash SPD system; pad columns zeroed.
 hipError_t gen_spd_f64(int64_t n, int64_t lda, int64_t row0, int64_t nrows, uint64_t seed,
                        double *A, double *b, hipStream_t s);
+// CGX_A_F32: A_ij = (float) of gen_spd_f64's value (round to nearest), b as gen_spd_f64's.
+hipError_t gen_spd_a32(int64_t n, int64_t lda, int64_t row0, int64_t nrows, uint64_t seed, float *A, double *b,
+                       hipStream_t s);
 // out = sum_{q<cnt} (8-byte slot q of in), in q order (one thread): rank-ordered combine.
 hipError_t sum_ordered_f64(const double *in, int cnt, double *out, hipStream_t s);
 
@@ -278,11 +293,14 @@ hipError_t preload_vector();
 hipError_t preload_poisson();
 hipError_t preload_ref_f32();
 hipError_t preload_symv();
-enum PreloadSet : unsigned { PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16 };
+hipError_t preload_matvec_a32();
+enum PreloadSet : unsigned {
+    PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32
+};
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
-        {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}};
+        {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

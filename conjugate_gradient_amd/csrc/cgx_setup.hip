@@ -23,6 +23,7 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
         if (c->op == OP_POISSON) set |= PL_POISSON;
         else if (f32ref(c)) set |= PL_REF_F32;
         else if (c->flags & CGX_SYMMETRIC) set |= PL_SYMV;
+        else if (a32(c)) set |= PL_MATVEC_A32;
         else set |= PL_MATVEC;
         HIPT(preload_kernels(set));
     }
@@ -32,7 +33,7 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
     HIPT(hipEventCreateWithFlags(&s.ev_sync2, hipEventDisableTiming));
     HIPT(hipEventCreateWithFlags(&s.ev_root, hipEventDisableTiming));
     if (!s.ev_pready) HIPT(hipEventCreateWithFlags(&s.ev_pready, hipEventDisableTiming));
-    const size_t abytes = (size_t)s.nloc * (size_t)c->lda * es;
+    const size_t abytes = (size_t)s.nloc * (size_t)c->lda * (size_t)c->aes;
     auto dmalloc = [&](char **p, size_t bytes) -> int {
         if (bytes == 0) bytes = 16;
         hipError_t e = hipMalloc(p, bytes);
@@ -198,7 +199,9 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
     if (c->mode == M_RCCL)
         for (auto &e : s.ev_prog)  // liveness only: the host asks whether the stream got this far
             HIPT(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
-    if (!f32ref(c) && c->op == OP_DENSE && !(c->flags & CGX_SYMMETRIC)) {
+    if (a32(c)) {
+        s.plan = plan_matvec_a32(s.dev, s.nloc, 0, 0, -1, 0, c->lda);
+    } else if (!f32ref(c) && c->op == OP_DENSE && !(c->flags & CGX_SYMMETRIC)) {
         s.plan = plan_matvec_f64(s.dev, s.nloc, 0, 0, -1, 0, c->lda);
         if (small_matvec(c)) s.plan = plan_matvec_small_f64(s.dev, s.nloc, c->lda);
     }
@@ -270,10 +273,11 @@ cgx_ctx *new_ctx(int64_t n, int nranks, int flags) {
     cgx_ctx *c = new (std::nothrow) cgx_ctx();
     if (!c) return nullptr;
     c->n = n;
-    c->lda = round_up(n, 128);
+    c->lda = round_up(n, (flags & CGX_A_F32) ? 256 : 128);  // k_matvec_a32's chunk is 256 columns
     c->nranks = nranks;
     c->flags = flags;
     c->es = (flags & CGX_F32_REF) ? 4 : 8;
+    c->aes = (flags & CGX_A_F32) ? 4 : c->es;
     return c;
 }
 
@@ -326,7 +330,7 @@ constexpr int64_t kFoldPMax = 2048;
 // matVec stages p in LDS (k_matvec_small_f64, every form of the iteration).
 bool small_matvec(const cgx_ctx *c) {
     if (c->mode != M_SINGLE || c->sh.size() != 1 || c->op != OP_DENSE || f32ref(c)) return false;
-    if (c->flags & (CGX_SYMMETRIC | CGX_HOST_STREAM)) return false;
+    if (c->flags & (CGX_SYMMETRIC | CGX_HOST_STREAM | CGX_A_F32)) return false;  // not ported to float A
     return plan_matvec_small_f64(c->sh[0].dev, c->sh[0].nloc, c->lda).small > 0;
 }
 
@@ -368,7 +372,8 @@ int finish_create(cgx_ctx *c, cgx_ctx **out) {
     c->fused_p = can_fuse_p(c);
     {  // the folded form of the two-launch iteration (CGX_FOLD_P=0 / 1: never / at any fused n)
         const char *e = std::getenv("CGX_FOLD_P");
-        c->fold_p = c->fused_p && (e && *e ? *e == '1' : c->n <= kFoldPMax || small_matvec(c));
+        c->fold_p = c->fused_p && !a32(c) &&  // the folded matVec is not ported to float A
+                    (e && *e ? *e == '1' : c->n <= kFoldPMax || small_matvec(c));
     }
     c->ref_mv_dot = can_fuse_ref_dot(c);
     c->ref_fused = c->ref_mv_dot && c->mode == M_SINGLE;
@@ -433,7 +438,18 @@ static int check_device(int device) {
 
 // Operator-generic constructors.  Dense: n unknowns, row blocks of n/P rows.
 // Poisson: n = m*m unknowns, slabs of m/P grid rows (n/P unknowns).
-static int check_op(int op, int64_t n, int64_t m, int parts, int flags) {
+// multi: cgx_create_multi / cgx_create_rank (and their Poisson forms), whatever the row block count.
+static int check_op(int op, int64_t n, int64_t m, int parts, int flags, bool multi = false) {
+    if (flags & CGX_A_F32) {  // one GPU, resident row-major A, fp64 arithmetic (+ CGX_TIMING)
+        const char *why = op == OP_POISSON           ? "the Poisson operator is matrix-free"
+                          : multi                    ? "one GPU only (cgx_create), not cgx_create_multi / cgx_create_rank"
+                          : (flags & CGX_F32_REF)    ? "not with CGX_F32_REF"
+                          : (flags & CGX_SYMMETRIC)  ? "not with CGX_SYMMETRIC"
+                          : (flags & CGX_HOST_STREAM) ? "not with CGX_HOST_STREAM"
+                          : (flags & CGX_PHASES)     ? "not with CGX_PHASES"
+                                                     : nullptr;
+        if (why) return fail(CGX_ERR_ARG, "CGX_A_F32: %s", why);
+    }
     if ((flags & CGX_PHASES) && (op != OP_DENSE || (flags & (CGX_F32_REF | CGX_HOST_STREAM | CGX_SYMMETRIC))))
         return fail(CGX_ERR_ARG, "CGX_PHASES: the dense fp64 operator with A resident (row-major) only");
     if (op == OP_POISSON) {
@@ -477,7 +493,7 @@ static int create_multi(cgx_ctx **ctx, int op, int64_t n, int64_t m, int nshards
     if (!ctx || !devices) return fail(CGX_ERR_ARG, "ctx/devices is NULL");
     *ctx = nullptr;
     if (nshards < 1 || nshards > kMaxShards) return fail(CGX_ERR_ARG, "nshards must be in [1, %d]", kMaxShards);
-    TRY(check_op(op, n, m, nshards, flags));
+    TRY(check_op(op, n, m, nshards, flags, /*multi=*/true));
     for (int i = 0; i < nshards; ++i) TRY(check_device(devices[i]));
     cgx_ctx *c = new_ctx_op(op, n, m, nshards, flags);
     if (!c) return fail(CGX_ERR_NOMEM, "host allocation failed");
@@ -533,7 +549,7 @@ static int create_rank(cgx_ctx **ctx, int op, int64_t n, int64_t m, int rank, in
                        int device, int flags) {
     if (!ctx || !id) return fail(CGX_ERR_ARG, "ctx/id is NULL");
     *ctx = nullptr;
-    TRY(check_op(op, n, m, nranks, flags));
+    TRY(check_op(op, n, m, nranks, flags, /*multi=*/true));
     if (rank < 0 || rank >= nranks) return fail(CGX_ERR_ARG, "rank %d not in [0, %d)", rank, nranks);
     if (nranks > S_TR - S_GATHER) return fail(CGX_ERR_ARG, "at most %d ranks", S_TR - S_GATHER);
     TRY(check_device(device));
@@ -696,7 +712,7 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
     for (auto &s : c->sh) info->nrows += s.nloc;
     info->flags = c->flags | (c->overlap ? CGX_OVERLAP_ACTIVE : 0) |
                   ((c->fused || c->fused_p || c->ref_fused) ? CGX_FUSED_ACTIVE : 0) | (c->peer ? CGX_PEER_ACTIVE : 0) |
-                  (c->sh[0].plan.small ? CGX_SMALL_ACTIVE : 0) | (c->fold_p ? CGX_FOLD_ACTIVE : 0) |
+                  ((c->sh[0].plan.small && !a32(c)) ? CGX_SMALL_ACTIVE : 0) | (c->fold_p ? CGX_FOLD_ACTIVE : 0) |
                   (c->xdefer ? CGX_XDEFER_ACTIVE : 0) |
                   (c->xd == 3 ? CGX_XDEFER3_ACTIVE : 0) |
                   ((c->mode == M_LOCAL && c->xchg_kernels) ? CGX_PULL_ACTIVE : 0) |
@@ -748,7 +764,7 @@ int cgx_set_rows(cgx_ctx *c, int64_t row0, int64_t nrows, const void *A_rows, in
                     (long long)(row0 + nrows), (long long)c->n);
     if (A_rows && c->op == OP_POISSON) return fail(CGX_ERR_ARG, "the Poisson operator is matrix-free: A must be NULL");
     if (A_rows && lda_host < c->n) return fail(CGX_ERR_ARG, "lda_host (%lld) < n", (long long)lda_host);
-    const size_t es = (size_t)c->es;
+    const size_t es = (size_t)c->es, aes = (size_t)c->aes;  // vectors / A (CGX_A_F32: 8 / 4)
     // A host-streamed A is rewritten in place on the host: first let every
     // copy (and kernel) still reading it from enqueued iterations finish.
     if (A_rows && (c->flags & CGX_HOST_STREAM)) TRY(sync_all(c));
@@ -794,13 +810,13 @@ int cgx_set_rows(cgx_ctx *c, int64_t row0, int64_t nrows, const void *A_rows, in
         } else if (A_rows && lda_host == c->lda && c->lda == c->n) {
             // same row pitch on both sides: one contiguous copy (a pitched copy
             // of the same bytes ran at a third of the rate from pinned memory)
-            HIPT(hipMemcpyAsync(s.A + (size_t)(lo - s.row0) * c->lda * es,
-                                static_cast<const char *>(A_rows) + (size_t)(lo - row0) * lda_host * es,
-                                (size_t)(hi - lo) * c->lda * es, hipMemcpyHostToDevice, s.stream));
+            HIPT(hipMemcpyAsync(s.A + (size_t)(lo - s.row0) * c->lda * aes,
+                                static_cast<const char *>(A_rows) + (size_t)(lo - row0) * lda_host * aes,
+                                (size_t)(hi - lo) * c->lda * aes, hipMemcpyHostToDevice, s.stream));
         } else if (A_rows)
-            HIPT(hipMemcpy2DAsync(s.A + (size_t)(lo - s.row0) * c->lda * es, (size_t)c->lda * es,
-                                  static_cast<const char *>(A_rows) + (size_t)(lo - row0) * lda_host * es,
-                                  (size_t)lda_host * es, (size_t)c->n * es, (size_t)(hi - lo), hipMemcpyHostToDevice,
+            HIPT(hipMemcpy2DAsync(s.A + (size_t)(lo - s.row0) * c->lda * aes, (size_t)c->lda * aes,
+                                  static_cast<const char *>(A_rows) + (size_t)(lo - row0) * lda_host * aes,
+                                  (size_t)lda_host * aes, (size_t)c->n * aes, (size_t)(hi - lo), hipMemcpyHostToDevice,
                                   s.stream));
         if (b_rows)
             HIPT(hipMemcpyAsync(s.b + (lo - s.row0) * es, static_cast<const char *>(b_rows) + (lo - row0) * es,
@@ -871,6 +887,9 @@ int cgx_generate_spd(cgx_ctx *c, uint64_t seed) {
         } else if (f32ref(c)) {
             HIPT(gen_spd_f32(c->n, c->lda, s.row0, s.nloc, seed, reinterpret_cast<float *>(s.A),
                              reinterpret_cast<float *>(s.b), s.stream));
+        } else if (a32(c)) {
+            HIPT(gen_spd_a32(c->n, c->lda, s.row0, s.nloc, seed, reinterpret_cast<float *>(s.A),
+                             reinterpret_cast<double *>(s.b), s.stream));
         } else {
             HIPT(gen_spd_f64(c->n, c->lda, s.row0, s.nloc, seed, reinterpret_cast<double *>(s.A),
                              reinterpret_cast<double *>(s.b), s.stream));

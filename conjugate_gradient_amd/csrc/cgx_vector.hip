@@ -415,9 +415,10 @@ __global__ __launch_bounds__(kNT) void k_dot_f64(int64_t n, const double *__rest
 // counter-hash SPD generator (generateSPDmatrix.m:4-17 distribution)
 // ---------------------------------------------------------------------------
 
-template <typename T>
+// T: A's element type, TB: b's (CGX_A_F32: float A beside double b)
+template <typename T, typename TB = T>
 __global__ __launch_bounds__(kNT) void k_gen_spd(int64_t n, int64_t lda, int64_t row0, int64_t nrows,
-                                                 uint64_t salt, uint64_t salt_b, T *A, T *b) {
+                                                 uint64_t salt, uint64_t salt_b, T *A, TB *b) {
 #pragma clang fp contract(off)
     for (int64_t rr = blockIdx.x; rr < nrows; rr += gridDim.x) {
         const uint64_t i = (uint64_t)(row0 + rr);
@@ -433,7 +434,7 @@ __global__ __launch_bounds__(kNT) void k_gen_spd(int64_t n, int64_t lda, int64_t
         }
         if (threadIdx.x == 0) {
             const uint64_t h = mix64(i ^ salt_b);
-            b[rr] = (T)((double)(h >> 11) * 0x1.0p-53);
+            b[rr] = (TB)((double)(h >> 11) * 0x1.0p-53);
         }
     }
 }
@@ -665,6 +666,14 @@ hipError_t gen_spd_f32(int64_t n, int64_t lda, int64_t row0, int64_t nrows, uint
                        float *b, hipStream_t s) {
     if (nrows <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_gen_spd<float>, dim3(grid_1d(nrows, 1, 65536)), dim3(kNT), 0, s, n, lda, row0,
+                       nrows, mix64(seed), mix64(seed + 1), A, b);
+    return hipGetLastError();
+}
+
+hipError_t gen_spd_a32(int64_t n, int64_t lda, int64_t row0, int64_t nrows, uint64_t seed, float *A, double *b,
+                       hipStream_t s) {
+    if (nrows <= 0) return hipSuccess;
+    hipLaunchKernelGGL((k_gen_spd<float, double>), dim3(grid_1d(nrows, 1, 65536)), dim3(kNT), 0, s, n, lda, row0,
                        nrows, mix64(seed), mix64(seed + 1), A, b);
     return hipGetLastError();
 }

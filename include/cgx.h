@@ -39,6 +39,31 @@
  *                doubling); point-to-point_cg.c with CGX_COMM_P2P (rank-order
  *                allSum).  Pinned by mpiexec runs of the unmodified programs
  *                (tests/golden/mpi/).
+ *   CGX_A_F32    A stored as float, everything else double: the fp64 solve of
+ *                the float matrix the reference's input paths hold
+ *                (fscanf("%f"), float *A, MPI_FLOAT) at half the matVec bytes.
+ *                - A lives on the device as float, pitch cgx_info.lda floats
+ *                  (n rounded up to 256), zero padded.  b, x, r, p, Ap and
+ *                  every scalar are double; cgx_info.elem_bytes stays 8 and
+ *                  cgx_info.flags carries CGX_A_F32.
+ *                - Each a_ij is widened to double inside the kernel (exact)
+ *                  and multiplied by p_j with an fp64 FMA; there is no fp32
+ *                  arithmetic anywhere.
+ *                - Row sums and the fused p.Ap are deterministic fixed-order
+ *                  sums, bit-identical for every (R, U, load policy) plan of
+ *                  the kernel.  The order differs from k_matvec_f64's:
+ *                  results agree with CGX_F64 on the same values to fp64
+ *                  rounding (the CGX_SYMMETRIC contract).
+ *                - Host side: A_rows / A of cgx_set_rows, cgx_set_system and
+ *                  cgx_conjugrad are `const float *` and lda_host counts
+ *                  floats; b and x stay double.
+ *                - cgx_generate_spd stores (float) of the value the fp64
+ *                  generator computes for A_ij (round to nearest); b as in
+ *                  fp64 mode.
+ *                - One GPU (cgx_create), resident row-major A, optionally
+ *                  CGX_TIMING.  CGX_ERR_ARG with CGX_F32_REF, CGX_SYMMETRIC,
+ *                  CGX_HOST_STREAM, CGX_PHASES, cgx_create_multi,
+ *                  cgx_create_rank and the Poisson constructors.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -57,7 +82,8 @@
 extern "C" {
 #endif
 
-#define CGX_VERSION 101 /* 0.1.1: cgx_overlap_info gained the end-to-end form times */
+#define CGX_VERSION 101 /* 0.1.1: cgx_overlap_info gained the end-to-end form times; CGX_A_F32 added (a new
+                           flag bit: no existing call changes meaning) */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -72,6 +98,7 @@ extern "C" {
 /* ---- flags ---------------------------------------------------------------- */
 #define CGX_F64          0x0   /* double data (default)                        */
 #define CGX_F32_REF      0x1   /* float data, bit-exact serialConjugate.c order */
+#define CGX_A_F32        0x2   /* float A, double vectors and arithmetic (above) */
 #define CGX_TIMING       0x100 /* time every matVec launch with HIP events      */
 #define CGX_NO_OVERLAP   0x400 /* multi-shard dense fp64: do not overlap the p
                                   exchange with the own-column-block matVec
@@ -180,14 +207,15 @@ typedef struct { char bytes[128]; } cgx_unique_id;
 
 typedef struct {
     int64_t n;            /* global system size                               */
-    int64_t lda;          /* device leading dimension (n rounded up to 128)   */
+    int64_t lda;          /* device leading dimension (n rounded up to 128;
+                             CGX_A_F32: to 256, in floats)                     */
     int     nranks;       /* row blocks in the whole job                      */
     int     nshards;      /* row blocks driven by this process                */
     int     rank0;        /* global index of this process's first row block   */
     int64_t row0;         /* first global row owned by this process           */
     int64_t nrows;        /* rows owned by this process                       */
     int     flags;
-    int     elem_bytes;   /* 8 (CGX_F64) or 4 (CGX_F32_REF)                   */
+    int     elem_bytes;   /* 8 (CGX_F64, CGX_A_F32) or 4 (CGX_F32_REF)        */
 } cgx_info;
 
 typedef struct {
@@ -349,7 +377,8 @@ int cgx_get_info(const cgx_ctx *ctx, cgx_info *info);
 int cgx_get_comm_info(cgx_ctx *ctx, cgx_comm_info *info);
 int cgx_get_overlap_info(const cgx_ctx *ctx, cgx_overlap_info *info);
 
-/* ---- data in / out (host arrays; element type per flags) ----------------- */
+/* ---- data in / out (host arrays; element type per flags: double, float with
+ * CGX_F32_REF; with CGX_A_F32 A is float and b / x are double) ------------- */
 /* Rows [row0, row0+nrows) of A (row-major, host leading dimension lda_host),
  * of b and of x0.  Any pointer may be NULL.  Rows this process does not own
  * are ignored, so every rank may pass the full system (MPI_Scatter /
@@ -383,7 +412,8 @@ int cgx_solve(cgx_ctx *ctx, void *x_inout, double eps, int64_t max_iter, cgx_sta
  * literal function-level drop-in: `conjugrad(A, b, x);` becomes
  * `cgx_conjugrad(A, b, x, ROWS, CGX_F32_REF, 1.0e-6, -1, NULL);`.  Host
  * arrays as the reference passes them (A row-major n x n, b, x in / out;
- * float with CGX_F32_REF -- the reference's x bit for bit -- else double),
+ * float with CGX_F32_REF -- the reference's x bit for bit -- else double;
+ * CGX_A_F32: the reference's float A beside double b and x),
  * one context on device 0 created, used and destroyed inside the call; st
  * may be NULL.  Repeated solves on one system: the context functions above. */
 int cgx_conjugrad(const void *A, const void *b, void *x, int64_t n, int flags, double eps, int64_t max_iter,
@@ -409,7 +439,12 @@ void *cgx_stream(cgx_ctx *ctx);
  * in tools/microbench/matvec_variants.hip),
  * resident blocks per CU for the grid (<= 0: occupancy query).  Results do not
  * depend on the plan's R/U/policy; the p.Ap partial order depends on the grid
- * size. */
+ * size.
+ * CGX_A_F32 contexts (k_matvec_a32): exactly the instantiated plans -- (rows
+ * per wave, 256-column chunks in flight) one of (1,4) (1,8) (2,4) (4,2) (4,4)
+ * (8,2), load policy 2 (default-policy loads) or 8 (non-temporal), both
+ * software-pipelined; anything else is CGX_ERR_ARG.  The same row sums bit
+ * for bit under every one of them. */
 int cgx_set_matvec_plan(cgx_ctx *ctx, int rows_per_wave, int chunks_in_flight, int nontemporal,
                         int blocks_per_cu);
 int cgx_get_matvec_plan(cgx_ctx *ctx, int *rows_per_wave, int *chunks_in_flight, int *nontemporal,
@@ -419,7 +454,8 @@ int cgx_get_matvec_plan(cgx_ctx *ctx, int *rows_per_wave, int *chunks_in_flight,
 int cgx_residual_norm(cgx_ctx *ctx, double *rnorm, double *bnorm);
 
 /* ---- kernel-level entry points (device pointers; unit parity) -------------- */
-/* dtype: CGX_F64 or CGX_F32_REF.  stream: hipStream_t or NULL.
+/* dtype: CGX_F64 or CGX_F32_REF (cgx_matvec also: CGX_A_F32).  stream:
+ * hipStream_t or NULL.
  * The reducing calls (cgx_dot, cgx_residual, cgx_update_xr) share one
  * reduction workspace per device: issue them on one stream per device (or
  * order the streams), as the reference's single-threaded calls are ordered. */
@@ -428,7 +464,8 @@ int cgx_dev_free(void *ptr);
 int cgx_memcpy_h2d(void *dst, const void *src, size_t bytes);
 int cgx_memcpy_d2h(void *dst, const void *src, size_t bytes);
 int cgx_dev_synchronize(void);
-/* matVec: out[i] = sum_j A[i*lda + j] * v[j], i < rows, j < cols. */
+/* matVec: out[i] = sum_j A[i*lda + j] * v[j], i < rows, j < cols.
+ * CGX_A_F32: A is float (lda in floats), v and out are double. */
 int cgx_matvec(int dtype, const void *A, int64_t lda, int64_t rows, int64_t cols,
                const void *v, void *out, void *stream);
 /* vecVec: *out_dev = a . b */

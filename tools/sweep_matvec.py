@@ -5,6 +5,15 @@ A loads, resident blocks per CU) on one GPU, interleaved rounds in one process
 the median / min matVec kernel time (HIP events) and algorithmic GB/s.
 
   python tools/sweep_matvec.py [--n 65536] [--rounds 3] [--iters 4]
+
+--a-fp32: the CGX_A_F32 kernel's plans (float A, fp64 arithmetic) instead, with
+the CGX_F64 default plan in the same rounds on the same generated system;
+GB/s on the bytes each algorithm needs (4 N^2 + 16 N against 8 N^2 + 16 N).
+Then one fixed-count run of 20 iterations per mode, bracketed by synchronize,
+for iterations/s, and -- the correctness cross-check at the timed size -- a
+solve to 1e-10 under CGX_A_F32 with its true residual.
+
+  python tools/sweep_matvec.py --a-fp32 [--n 65536] [--rounds 5] [--iters 4]
 """
 import argparse
 import itertools
@@ -12,9 +21,79 @@ import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import conjugate_gradient_amd as cg  # noqa: E402
+
+A32_PLANS = [(1, 4), (1, 8), (2, 4), (4, 2), (4, 4), (8, 2)]
+
+
+def time_plan(s, plan, iters):
+    """ms per matVec launch (CGX_TIMING events) of `iters` fixed iterations under `plan` (None: as is)."""
+    if plan is not None:
+        s.set_matvec_plan(*plan)
+    s.iterate(1, eps=-1.0)  # warm this plan
+    s.reset_timing()
+    s.iterate(iters, eps=-1.0)
+    st = s.stats()
+    return st.matvec_ms / st.matvec_count
+
+
+def sweep_a32(args):
+    n = args.n
+    s64 = cg.Solver(n, flags=cg.CGX_F64 | cg.CGX_TIMING)
+    s32 = cg.Solver(n, flags=cg.CGX_A_F32 | cg.CGX_TIMING)
+    for s in (s64, s32):
+        s.generate_spd(42)
+        s.begin()
+    nts = [int(v) for v in args.nt.split(",")] if args.nt != "0,1" else [2, 8]
+    configs = [(R, U, nt, 0) for (R, U) in A32_PLANS for nt in nts]
+    times = {c: [] for c in configs}
+    times["f64"] = []
+    plans = {"f64": s64.matvec_plan()}
+    for _ in range(args.rounds):
+        times["f64"].append(time_plan(s64, None, args.iters))
+        for c in configs:
+            times[c].append(time_plan(s32, c, args.iters))
+            plans[c] = s32.matvec_plan()
+    rows = []
+    for c, t in times.items():
+        nbytes = (8 if c == "f64" else 4) * n * n + 16 * n
+        med, mn, mx = statistics.median(t), min(t), max(t)
+        pl = plans[c]
+        rows.append({"mode": "CGX_F64" if c == "f64" else "CGX_A_F32", "n": n, "R": pl["R"], "U": pl["U"], "nt": pl["nt"],
+                     "blocks": pl["blocks"], "rounds": len(t), "ms_med": med, "ms_min": mn, "ms_max": mx,
+                     "bytes": nbytes, "gbps_med": nbytes / med / 1e6, "gbps_best": nbytes / mn / 1e6})
+    rows.sort(key=lambda r: r["ms_med"])
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    best = next(r for r in rows if r["mode"] == "CGX_A_F32")
+    # iterations/s: 20 fixed iterations per mode (twice, alternating), the A_F32 context on the sweep's best plan
+    for name, s, plan in (("CGX_F64", s64, None), ("CGX_A_F32 best", s32, (best["R"], best["U"], best["nt"], 0)),
+                          ("CGX_F64", s64, None), ("CGX_A_F32 best", s32, (best["R"], best["U"], best["nt"], 0))):
+        if plan is not None:
+            s.set_matvec_plan(*plan)
+        s.generate_spd(42)
+        s.begin()
+        s.iterate(3, eps=-1.0)
+        s.synchronize()
+        t0 = time.perf_counter()
+        s.iterate(20, eps=-1.0)
+        s.synchronize()
+        dt = time.perf_counter() - t0
+        print(json.dumps({"mode": name, "n": n, "plan": s.matvec_plan(), "fixed_iterations": 20,
+                          "ms_per_iteration": dt / 20 * 1e3, "iterations_per_s": 20 / dt}), flush=True)
+    s64.close()
+    s32.close()
+    # the default plan of a fresh context, and the correctness cross-check at the timed size
+    with cg.Solver(n, flags=cg.CGX_A_F32) as s:
+        s.generate_spd(42)
+        x, st = s.solve(None, eps=1e-10)
+        rn, bn = s.residual_norm()
+        print(json.dumps({"mode": "CGX_A_F32 default", "n": n, "plan": s.matvec_plan(), "solve_eps": 1e-10,
+                          "iterations": st.iterations, "converged": st.converged, "solve_ms": st.solve_ms,
+                          "residual_norm": rn, "b_norm": bn, "residual_below_stop": bool(rn < 1e-10 * bn)}), flush=True)
 
 
 def main():
@@ -26,7 +105,10 @@ def main():
     ap.add_argument("--U", default="2,4,8")
     ap.add_argument("--nt", default="0,1")
     ap.add_argument("--bpc", default="0")
+    ap.add_argument("--a-fp32", action="store_true", help="the CGX_A_F32 plans beside the CGX_F64 default")
     args = ap.parse_args()
+    if args.a_fp32:
+        return sweep_a32(args)
     n = args.n
     s = cg.Solver(n, flags=cg.CGX_F64 | cg.CGX_TIMING)
     s.generate_spd(42)
