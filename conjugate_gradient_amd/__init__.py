@@ -37,6 +37,7 @@ __all__ = [
     "PHASE_NAMES", "overlap_rule", "CgxError", "Stats",
     "Solver", "lib", "build",
     "device_pci_bus_id", "device_link",
+    "CGX_MAX_NRHS", "matVec_nrhs",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
     "count_text", "read_dims", "device_count", "get_unique_id", "DeviceArray",
 ]
@@ -63,6 +64,7 @@ CGX_FOLDED_ACTIVE = 0x800000
 CGX_HALO_PULL_ACTIVE = 0x1000000
 CGX_THREADS_ACTIVE = 0x2000000
 CGX_HALO_OVERLAP_ACTIVE = 0x4000000
+CGX_MAX_NRHS = 8  # cgx_create_nrhs: systems solved together on one matrix
 
 # cgx_phase_times indices (include/cgx.h), in the order the phases tile an iteration
 PHASE_NAMES = ("matvec_own", "gather_exposed", "matvec", "combine_pap", "update_r", "combine_rr", "update_xp",
@@ -163,6 +165,11 @@ def lib() -> ctypes.CDLL:
         "cgx_get_phase_times": ([vp, ctypes.POINTER(PhaseTimes)], i32),
         "cgx_create": ([pctx, i64, i32, i32], i32),
         "cgx_create_multi": ([pctx, i64, i32, ctypes.POINTER(i32), i32], i32),
+        "cgx_create_nrhs": ([pctx, i64, i32, i32, i32], i32),
+        "cgx_get_nrhs": ([vp, ctypes.POINTER(i32)], i32),
+        "cgx_get_stats_rhs": ([vp, i32, ctypes.POINTER(Stats)], i32),
+        "cgx_residual_norms": ([vp, ctypes.POINTER(f64), ctypes.POINTER(f64)], i32),
+        "cgx_matvec_nrhs": ([vp, i64, i64, i64, i32, vp, i64, vp, i64, vp], i32),
         "cgx_get_unique_id": ([ctypes.POINTER(UniqueId)], i32),
         "cgx_rccl_available": ([], i32),
         "cgx_create_rank": ([pctx, i64, i32, i32, ctypes.POINTER(UniqueId), i32, i32], i32),
@@ -367,6 +374,24 @@ def matVec(A: DeviceArray, v: DeviceArray, out: DeviceArray, rows: int, cols: in
     _check(lib().cgx_matvec(dt, A.ptr, lda or cols, rows, cols, v.ptr, out.ptr, None), "cgx_matvec")
 
 
+def matVec_nrhs(A: DeviceArray, V: DeviceArray, Out: DeviceArray, rows: int, cols: int, nrhs: int,
+                lda: int | None = None, ldv: int | None = None, ldo: int | None = None, v_offset: int = 0) -> None:
+    """``nrhs`` matVecs in one pass over A (fp64): Out[j*ldo + i] = sum_c A[i*lda + c] * V[j*ldv + c].
+    Column j is :func:`matVec`'s result on column j of V bit for bit.  ``v_offset``: V starts that many
+    elements into its device array (an odd offset takes every column off the 16-byte grid)."""
+    lda, ldv, ldo = lda or cols, ldv or cols, ldo or rows
+    _need(1 <= nrhs <= CGX_MAX_NRHS, f"matVec_nrhs: nrhs must be in [1, {CGX_MAX_NRHS}] (got {nrhs})")
+    _need(rows >= 0 and cols >= 0 and lda >= cols and ldv >= cols and ldo >= rows and v_offset >= 0,
+          "matVec_nrhs: need rows, cols >= 0, lda >= cols, ldv >= cols and ldo >= rows")
+    _need(A.dtype == np.float64 and V.dtype == np.float64 and Out.dtype == np.float64, "matVec_nrhs: float64 only")
+    if rows and cols:
+        _fits([A], (rows - 1) * lda + cols, "matVec_nrhs A")
+        _fits([V], v_offset + (nrhs - 1) * ldv + cols, "matVec_nrhs V")
+        _fits([Out], (nrhs - 1) * ldo + rows, "matVec_nrhs Out")
+    _check(lib().cgx_matvec_nrhs(A.ptr, lda, rows, cols, nrhs, V.ptr + 8 * v_offset, ldv, Out.ptr, ldo, None),
+           "cgx_matvec_nrhs")
+
+
 def vecVec(a: DeviceArray, b: DeviceArray, out: DeviceArray, n: int | None = None) -> None:
     """serialConjugate.c:145-155: out[0] = a . b (device scalar)."""
     n = n if n is not None else a.count
@@ -412,13 +437,24 @@ class Solver:
     Arrays handed in are cast silently (``np.ascontiguousarray``) to the
     context's types: float32 under CGX_F32_REF, float64 otherwise; under
     CGX_A_F32 A is cast to float32 (a float64 A is rounded to nearest) while
-    b and x are cast to float64."""
+    b and x are cast to float64.
+
+    ``nrhs=K`` (1..CGX_MAX_NRHS; cgx_create_nrhs): K systems on one matrix solved
+    together, one read of A per iteration.  b and x arrays then have shape
+    ``(K, n)`` (also for K = 1), the vector arguments of ``set_rows`` shape
+    ``(K, nrows)``, and ``solve`` / ``get_x`` return ``(K, n)``."""
 
     def __init__(self, n: int, *, flags: int = CGX_F64, device: int = 0, devices=None,
                  rank: int | None = None, nranks: int | None = None, unique_id: bytes | None = None,
-                 poisson_m: int | None = None):
+                 poisson_m: int | None = None, nrhs: int | None = None):
         """Dense n x n system, or (poisson_m=m) the matrix-free 5-point Poisson
         operator on an m x m grid (n must then be m*m or None)."""
+        self.nrhs = None
+        if nrhs is not None:  # checked before any C call
+            _need(devices is None and rank is None and poisson_m is None,
+                  "Solver: nrhs runs on one GPU (not with devices=, rank= or poisson_m=)")
+            _need(isinstance(nrhs, (int, np.integer)) and 1 <= nrhs <= CGX_MAX_NRHS,
+                  f"Solver: nrhs must be in [1, {CGX_MAX_NRHS}] (got {nrhs})")
         L = lib()
         self.poisson_m = poisson_m
         if poisson_m is not None:
@@ -446,10 +482,19 @@ class Solver:
         elif devices is not None:
             arr = (ctypes.c_int * len(devices))(*devices)
             rc = L.cgx_create_multi(ctypes.byref(h), self.n, len(devices), arr, flags)
+        elif nrhs is not None:
+            rc = L.cgx_create_nrhs(ctypes.byref(h), self.n, int(nrhs), device, flags)
+            self.nrhs = int(nrhs) if rc == 0 else None
         else:
             rc = L.cgx_create(ctypes.byref(h), self.n, device, flags)
-        _check(rc, "cgx_create")
+        _check(rc, "cgx_create_nrhs" if nrhs is not None else "cgx_create")
         self._h = h.value
+
+    def _vshape(self, rows: int | None = None) -> tuple:
+        """The shape of a b or x argument: (n,), or (nrhs, n) on an nrhs context."""
+        k = getattr(self, "nrhs", None)
+        m = self.n if rows is None else rows
+        return (m,) if k is None else (k, m)
 
     # lifetime
     def close(self) -> None:
@@ -488,16 +533,37 @@ class Solver:
     def set_system(self, A: np.ndarray, b: np.ndarray, x0: np.ndarray | None = None) -> None:
         A = np.ascontiguousarray(A, _a_dtype(self.flags))
         b = np.ascontiguousarray(b, self.dtype)
-        x0 = np.zeros(self.n, self.dtype) if x0 is None else np.ascontiguousarray(x0, self.dtype)
+        vs = self._vshape()
+        x0 = np.zeros(vs, self.dtype) if x0 is None else np.ascontiguousarray(x0, self.dtype)
         _need(A.shape == (self.n, self.n), f"set_system: A has shape {A.shape}, ({self.n}, {self.n}) needed")
-        _need(b.shape == (self.n,), f"set_system: b has shape {b.shape}, ({self.n},) needed")
-        _need(x0.shape == (self.n,), f"set_system: x0 has shape {x0.shape}, ({self.n},) needed")
+        _need(b.shape == vs, f"set_system: b has shape {b.shape}, {vs} needed")
+        _need(x0.shape == vs, f"set_system: x0 has shape {x0.shape}, {vs} needed")
         _check(lib().cgx_set_system(self._h, _ptr(A), _ptr(b), _ptr(x0)), "cgx_set_system")
 
     def set_rows(self, row0: int, A_rows=None, b_rows=None, x_rows=None) -> None:
         arrs = [None if a is None else np.ascontiguousarray(a, dt)
                 for a, dt in zip((A_rows, b_rows, x_rows), (_a_dtype(self.flags), self.dtype, self.dtype))]
         _need(any(a is not None for a in arrs), "set_rows: nothing to set")
+        k = getattr(self, "nrhs", None)
+        if k is not None:  # the vectors: (nrhs, nrows), system after system
+            for a, name in zip(arrs[1:], ("b_rows", "x_rows")):
+                if a is not None:
+                    _need(a.ndim == 2 and a.shape[0] == k,
+                          f"set_rows: {name} has shape {a.shape}, ({k}, nrows) needed")
+            nrows = arrs[0].shape[0] if arrs[0] is not None else next(a.shape[1] for a in arrs[1:] if a is not None)
+            if arrs[0] is not None:
+                _need(arrs[0].ndim == 2 and arrs[0].shape[1] >= self.n,
+                      f"set_rows: A_rows has shape {arrs[0].shape}, (nrows, >= {self.n}) needed")
+            for a, name in zip(arrs[1:], ("b_rows", "x_rows")):
+                if a is not None:
+                    _need(a.shape[1] == nrows,
+                          f"set_rows: {name} has shape {a.shape}; every argument needs the same {nrows} rows")
+            _need(0 <= row0 and row0 + nrows <= self.n,
+                  f"set_rows: rows [{row0}, {row0 + nrows}) outside [0, {self.n})")
+            lda = arrs[0].shape[1] if arrs[0] is not None else self.n
+            _check(lib().cgx_set_rows(self._h, row0, nrows, None if arrs[0] is None else _ptr(arrs[0]), lda,
+                                      *(None if a is None else _ptr(a) for a in arrs[1:])), "cgx_set_rows")
+            return
         nrows = next(a.shape[0] for a in arrs if a is not None)
         if arrs[0] is not None:
             _need(arrs[0].ndim == 2 and arrs[0].shape[1] >= self.n,
@@ -518,13 +584,13 @@ class Solver:
         _check(lib().cgx_generate_spd(self._h, seed), "cgx_generate_spd")
 
     def get_x(self) -> np.ndarray:
-        x = np.empty(self.n, self.dtype)
+        x = np.empty(self._vshape(), self.dtype)
         _check(lib().cgx_get_x(self._h, _ptr(x)), "cgx_get_x")
         return x
 
     def set_x(self, x: np.ndarray) -> None:
         x = np.ascontiguousarray(x, self.dtype)
-        _need(x.shape == (self.n,), f"set_x: x has shape {x.shape}, ({self.n},) needed")
+        _need(x.shape == self._vshape(), f"set_x: x has shape {x.shape}, {self._vshape()} needed")
         _check(lib().cgx_set_x(self._h, _ptr(x)), "cgx_set_x")
 
     # solve
@@ -532,7 +598,7 @@ class Solver:
         st = Stats()
         if x0 is not None:
             x = np.array(x0, dtype=self.dtype, copy=True)
-            _need(x.shape == (self.n,), f"solve: x0 has shape {x.shape}, ({self.n},) needed")
+            _need(x.shape == self._vshape(), f"solve: x0 has shape {x.shape}, {self._vshape()} needed")
             _check(lib().cgx_solve(self._h, _ptr(x), eps, max_iter, ctypes.byref(st)), "cgx_solve")
         else:
             _check(lib().cgx_solve(self._h, None, eps, max_iter, ctypes.byref(st)), "cgx_solve")
@@ -552,6 +618,22 @@ class Solver:
         st = Stats()
         _check(lib().cgx_get_stats(self._h, ctypes.byref(st)), "cgx_get_stats")
         return st
+
+    def stats_rhs(self, j: int) -> Stats:
+        """System j's iterations, converged and rr of the last solve (nrhs contexts; j = 0 otherwise)."""
+        k = getattr(self, "nrhs", None) or 1
+        _need(0 <= j < k, f"stats_rhs: system {j} not in [0, {k})")
+        st = Stats()
+        _check(lib().cgx_get_stats_rhs(self._h, j, ctypes.byref(st)), "cgx_get_stats_rhs")
+        return st
+
+    def residual_norms(self) -> tuple[np.ndarray, np.ndarray]:
+        """(||b_j - A x_j||, ||b_j||) per system for the current x (ends a solve in progress)."""
+        k = getattr(self, "nrhs", None) or 1
+        rn, bn = np.zeros(k), np.zeros(k)
+        pd = ctypes.POINTER(ctypes.c_double)
+        _check(lib().cgx_residual_norms(self._h, rn.ctypes.data_as(pd), bn.ctypes.data_as(pd)), "cgx_residual_norms")
+        return rn, bn
 
     def residual_norm(self) -> tuple[float, float]:
         """(||b - A x||, ||b||) for the current x (ends a solve in progress)."""

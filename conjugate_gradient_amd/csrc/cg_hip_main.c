@@ -31,7 +31,11 @@
  * bytes per matVec; CG's A is symmetric by contract, the lower triangle
  * outside the diagonal tiles is not read), --a-fp32 (one GPU: A parsed and
  * kept on the GPU as float, exactly what initialize() reads, with b, x0 and
- * all arithmetic in fp64 -- CGX_A_F32, half the bytes per matVec).
+ * all arithmetic in fp64 -- CGX_A_F32, half the bytes per matVec),
+ * --nrhs K (one GPU, fp64: K systems on the one matrix solved together, one
+ * read of A per iteration -- cgx_create_nrhs; vectorb and initialguess then
+ * hold K*N values, system after system, --print-x prints K*N lines, --stats
+ * adds one line per system, and --spd takes b_j from seed S + j).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -111,8 +115,9 @@ static void usage(const char *prog) {
     fprintf(stderr,
             "usage: %s [--gpus P [--p2p]] [--fp32-ref | --symmetric | --a-fp32] [--eps E] [--max-iter M] [--dims FILE] [--n N]\n"
             "          [--threads T] [--print-x] [--stats] matrixA vectorb initialguess\n"
-            "       %s --spd N [--seed S] [--gpus P] [--a-fp32] [--eps E] [--max-iter M] [--stats]\n",
-            prog, prog);
+            "       %s --spd N [--seed S] [--gpus P] [--a-fp32] [--eps E] [--max-iter M] [--stats]\n"
+            "       %s --nrhs K ... (one GPU, fp64: K systems on one matrix; vectorb and initialguess hold K*N values)\n",
+            prog, prog, prog);
 }
 
 static int die_cgx(int rc, const char *what) {
@@ -138,6 +143,7 @@ static int read_file(const char *path, int64_t count, int as_float, void *out, i
 typedef struct {
     int64_t n;
     int gpus, flags, rc;
+    int nrhs;  /* > 0: cgx_create_nrhs */
     cgx_ctx *ctx;
     double t_rt, t_done;  /* when the HIP runtime was up / creation finished (now_s) */
 } create_job;
@@ -147,7 +153,9 @@ static void *create_ctx(void *arg) {
     int ndev0 = 0;
     cgx_device_count(&ndev0); /* starts the HIP runtime */
     j->t_rt = now_s();
-    if (j->gpus == 1) {
+    if (j->nrhs > 0) {
+        j->rc = cgx_create_nrhs(&j->ctx, j->n, j->nrhs, 0, j->flags);
+    } else if (j->gpus == 1) {
         j->rc = cgx_create(&j->ctx, j->n, 0, j->flags);
     } else {
         int devs[32];
@@ -267,7 +275,7 @@ int main(int argc, char **argv) {
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
-    long long max_iter = -1, n_opt = -1, spd_n = -1;
+    long long max_iter = -1, n_opt = -1, spd_n = -1, nrhs = 0;
     unsigned long long seed = 42;
     const char *dims_path = NULL;
     const char *pos[3];
@@ -296,6 +304,9 @@ int main(int argc, char **argv) {
             threads = v < 1 ? 1 : (v > 256 ? 256 : (int)v);
         } else if (!strcmp(a, "--spd") && has_val) {
             if (!opt_ll(a, argv[++i], &spd_n)) return 2;
+        } else if (!strcmp(a, "--nrhs") && has_val) {
+            if (!opt_ll(a, argv[++i], &nrhs)) return 2;
+            if (nrhs < 1 || nrhs > CGX_MAX_NRHS) { fprintf(stderr, "--nrhs must be in [1, %d]\n", CGX_MAX_NRHS); return 2; }
         } else if (!strcmp(a, "--seed") && has_val) {
             if (!opt_ll(a, argv[++i], &v)) return 2;
             seed = (unsigned long long)v;
@@ -325,6 +336,11 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--a-fp32 is float A with fp64 arithmetic on one GPU (no --fp32-ref, no --symmetric, --gpus 1)\n");
         return 2;
     }
+    if (nrhs > 0 && (fp32ref || a_fp32 || symmetric || gpus != 1 || p2p)) {
+        fprintf(stderr, "--nrhs is fp64 on one GPU with A resident (no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p)\n");
+        return 2;
+    }
+    const int64_t nsys = nrhs > 0 ? nrhs : 1; /* systems: vectors of nsys * n values */
 
     /* ---- N ---------------------------------------------------------------- */
     int64_t n = 0;
@@ -339,6 +355,8 @@ int main(int argc, char **argv) {
     } else {
         n = cgx_text_count(pos[1]);
         if (n < 0) { printf("Could not open file\n"); fprintf(stderr, "%s: cannot open\n", pos[1]); return 1; }
+        if (n % nsys != 0) { fprintf(stderr, "%s: %lld values are not %lld systems\n", pos[1], (long long)n, (long long)nsys); return 1; }
+        n /= nsys;
     }
     if (n < 1) { fprintf(stderr, "empty system\n"); return 1; }
     if (n % gpus != 0) { printf("%lld is not divisible by %d\n", (long long)n, gpus); return 1; } /* parallel_cg.c:88 */
@@ -351,7 +369,8 @@ int main(int argc, char **argv) {
     const size_t es = fp32ref ? 4 : 8;           /* b, x */
     const size_t aes = a_fp32 ? 4 : es;          /* A: float with --a-fp32, as initialize() reads it */
     const int a_as_float = fp32ref || a_fp32;
-    void *x = malloc((size_t)n * es);
+    const size_t vlen = (size_t)(nsys * n); /* values in b and in x */
+    void *x = malloc(vlen * es);
     void *A = NULL, *b = NULL;
     /* static: the release thread may still read it while an error path
      * returns from main */
@@ -377,18 +396,18 @@ int main(int argc, char **argv) {
     const int stream_a = spd_n <= 0 && !(se && !strcmp(se, "0"));
     if (!x) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     if (spd_n > 0) {
-        memset(x, 0, (size_t)n * es);
+        memset(x, 0, vlen * es);
     } else if (stream_a) {
-        b = malloc((size_t)n * es);
+        b = malloc(vlen * es);
         if (!b) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     } else {
         /* initialize(A), initialize(b), initialize(x0): serialConjugate.c:65-67 */
         if (big_alloc(&Abuf, (size_t)n * (size_t)n * aes) != 0) A = NULL;
         else A = Abuf.p;
-        b = malloc((size_t)n * es);
+        b = malloc(vlen * es);
         if (!A || !b) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     }
-    create_job job = {n, gpus, flags, CGX_OK, NULL, 0.0, 0.0};
+    create_job job = {n, gpus, flags, CGX_OK, (int)nrhs, NULL, 0.0, 0.0};
     const double t_start = now_s();
     pthread_t creator;
     const int threaded = pthread_create(&creator, NULL, create_ctx, &job) == 0;
@@ -460,7 +479,8 @@ int main(int argc, char **argv) {
         } else if (threaded) {
             pthread_join(creator, NULL);
         }
-        if (!read_rc) read_rc = read_file(pos[1], n, fp32ref, b, threads) || read_file(pos[2], n, fp32ref, x, 1);
+        if (!read_rc)
+            read_rc = read_file(pos[1], (int64_t)vlen, fp32ref, b, threads) || read_file(pos[2], (int64_t)vlen, fp32ref, x, 1);
         rel.text = st.text;
         if (!defer_release) {
             if (pthread_create(&freer, NULL, release_buf, &rel) == 0) freeing = 1;
@@ -469,7 +489,8 @@ int main(int argc, char **argv) {
     } else {
         read_rc = spd_n > 0 ? 0
                             : (read_file(pos[0], n * n, a_as_float, A, threads) ||
-                               read_file(pos[1], n, fp32ref, b, threads) || read_file(pos[2], n, fp32ref, x, 1));
+                               read_file(pos[1], (int64_t)vlen, fp32ref, b, threads) ||
+                               read_file(pos[2], (int64_t)vlen, fp32ref, x, 1));
         t_parsed = now_s();
         if (threaded) pthread_join(creator, NULL);  /* before any exit: HIP may be starting up on it */
     }
@@ -533,8 +554,16 @@ int main(int argc, char **argv) {
     if (stats)
         printf("iterations: %lld converged: %d residual_norm: %.6e\n", (long long)st.iterations, st.converged,
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
+    if (stats && nrhs > 0)
+        for (int j = 0; j < (int)nrhs; ++j) {
+            cgx_stats sj;
+            rc = cgx_get_stats_rhs(ctx, j, &sj);
+            if (rc != CGX_OK) return die_cgx(rc, "cgx_get_stats_rhs");
+            printf("system %d iterations: %lld converged: %d residual_norm: %.6e\n", j, (long long)sj.iterations,
+                   sj.converged, sj.rr >= 0 ? __builtin_sqrt(sj.rr) : -1.0);
+        }
     if (print_x) {
-        for (int64_t i = 0; i < n; ++i) {
+        for (int64_t i = 0; i < (int64_t)vlen; ++i) {
             if (fp32ref) printf("%.9g\n", (double)((float *)x)[i]);
             else printf("%.17g\n", ((double *)x)[i]);
         }

@@ -3,6 +3,7 @@
 //   cgx_setup.hip     contexts and shards: create, destroy, data in and out
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
+//   cgx_nrhs.hip      cgx_create_nrhs contexts: several systems per pass over A
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
 //
@@ -244,6 +245,26 @@ struct Shard {
 
 namespace cgxh {
 struct LocalPool;  // cgx_local_mt.hip
+
+// cgx_create_nrhs (cgx_nrhs.hip): nrhs systems on one matrix, one read of A
+// per iteration.  The context's one shard holds A, the stream, the events and
+// the host-mapped record as a cgx_create context's; the vectors and scalars of
+// the nrhs systems live here.  Column j of b, x, r, p, Ap starts at j * lda
+// doubles (zero past n), so p is what k_matvec_nrhs_f64 multiplies.
+struct NrhsState {
+    int nrhs = 0;  // 1..CGX_MAX_NRHS
+    char *b = nullptr, *x = nullptr, *r = nullptr, *p = nullptr, *Ap = nullptr;
+    NrhsScal *sc = nullptr;     // device scalars and the per-column stopping record
+    NrhsScal *h_sc = nullptr;   // pinned copy for the host's reads
+    RedWs ws{nullptr, nullptr}; // kMaxNrhs * kMaxRedBlocks partials, kNrhsTickets counters
+    char *h_v = nullptr;        // pinned staging for cgx_get_x (null above kXStageMax)
+    MatvecPlan plan;
+    bool x_zero = true;         // every x_j is known to be all zeros
+    // the last solve's per-column outcome (cgx_get_stats_rhs)
+    int64_t iters[kMaxNrhs] = {};
+    int conv[kMaxNrhs] = {};
+    double rr[kMaxNrhs] = {};
+};
 }
 
 using namespace cgxh;
@@ -340,6 +361,8 @@ struct cgx_ctx {
     // LOCAL mode: one host thread per row block enqueues its block's iteration
     // (cgx_local_mt.hip); null when not used
     cgxh::LocalPool *pool = nullptr;
+    // cgx_create_nrhs: the nrhs systems' vectors and scalars (null in every other context)
+    cgxh::NrhsState *nr = nullptr;
     // CGX_PHASES: resolved per-iteration phase durations (us), cgx_phase_times' order;
     // the wall clock's rate, and the previous stamped iteration's first start /
     // last end (ticks; 0 = none) so the gap across a resolve is still measured
@@ -458,6 +481,20 @@ int launch_update_xp(const cgx_ctx *c, const Shard &s, int64_t k, XpForm form, d
 int do_iteration(cgx_ctx *c, double eps, int *stop, bool gated = false);
 bool warm_eligible(const cgx_ctx *c);
 int warm_solve_kernels(cgx_ctx *c);
+// cgx_nrhs.hip: the nrhs context's own paths; the entry points of the other
+// files branch to them at their top (c->nr != nullptr)
+int nrhs_check_args(int nrhs, int flags);
+int nrhs_alloc(cgx_ctx *c, int nrhs);
+void nrhs_free(cgx_ctx *c);
+int nrhs_set_vec_rows(cgx_ctx *c, int64_t row0, int64_t nrows, const void *b_rows, const void *x_rows);
+int nrhs_get_x(cgx_ctx *c, void *x);
+int nrhs_fill(cgx_ctx *c, double b_value, double x_value);
+int nrhs_generate_b(cgx_ctx *c, uint64_t seed);
+int nrhs_begin(cgx_ctx *c);
+int nrhs_iterate(cgx_ctx *c, int64_t count, double eps, int64_t *done, int *converged);
+int nrhs_solve(cgx_ctx *c, void *x_inout, double eps, int64_t max_iter, cgx_stats *st);
+int nrhs_get_stats(cgx_ctx *c, cgx_stats *st);
+int nrhs_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu);
 // cgx_api.hip
 int dev_ws(RedWs *out);
 int check_dtype(int dtype, bool matvec = false);  // matvec: CGX_A_F32 is a dtype too

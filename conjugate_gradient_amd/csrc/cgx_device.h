@@ -198,6 +198,84 @@ __device__ __forceinline__ void grid_sum_last_block(double v, double *partials, 
     }
 }
 
+// K sums in one hand-off (the nrhs kernels, cgx_matvec_nrhs.hip): column j's
+// partials live in partials[j * kMaxRedBlocks + block], one ticket serves all
+// K, and out[j] is written only where bit j of `mask` is set.  Each column is
+// summed exactly as grid_sum_last_block sums its one value (wave sum, the
+// block's waves in order, the partials in its order), so a column's result
+// does not depend on K or on which column it is.  The storing lane writes its
+// K partials write-through and drains them all before the ticket
+// (kHandoffNote).
+template <int K, int NT = kNT>
+__device__ __forceinline__ void grid_sum_last_block_n(const double (&v)[K], double *partials, unsigned *ticket,
+                                                      double *out, unsigned mask) {
+    __shared__ double red[K][NT / 64];
+    __shared__ int is_last;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double s = wave_sum(v[j]);
+        if (lane == 0) red[j][wid] = s;
+    }
+    __syncthreads();
+    if (gridDim.x == 1) {  // as grid_sum_last_block's one-block form
+        if (threadIdx.x < K) {
+            const int j = threadIdx.x;
+            double t = red[j][0];
+#pragma unroll
+            for (int w = 1; w < NT / 64; ++w) t += red[j][w];
+            t = 0.0 + t;
+            if ((mask >> j) & 1u) out[j] = t;
+        }
+        return;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            double t = red[j][0];
+#pragma unroll
+            for (int w = 1; w < NT / 64; ++w) t += red[j][w];
+            __hip_atomic_store(partials + (size_t)j * kMaxRedBlocks + blockIdx.x, t, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        is_last = (prev == gridDim.x - 1);
+    }
+    __syncthreads();  // every read of red[] above is done
+    if (!is_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double *pj = partials + (size_t)j * kMaxRedBlocks;
+        double s = 0.0;
+        for (unsigned i0 = threadIdx.x; i0 < gridDim.x; i0 += 8 * NT) {
+            double pv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const unsigned i = i0 + u * NT;
+                pv[u] = (i < gridDim.x) ? __hip_atomic_load(pj + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (i0 + u * NT < gridDim.x) s += pv[u];
+        }
+        s = wave_sum(s);
+        if (lane == 0) red[j][wid] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            double t = red[j][0];
+#pragma unroll
+            for (int w = 1; w < NT / 64; ++w) t += red[j][w];
+            if ((mask >> j) & 1u) out[j] = t;
+        }
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // grid_sum_last_block's hand-off, but the last block keeps going: returns
 // true (block-uniform) in the block that summed the partials, with the total
 // in `total` for every thread of it; *out gets the total as well.  The bytes

@@ -581,6 +581,7 @@ int do_iteration(cgx_ctx *c, double eps, int *stop, bool gated) {
 constexpr int64_t kWarmMaxN = 16384;
 bool warm_eligible(const cgx_ctx *c) {
     if (c->mode != M_SINGLE || c->op != OP_DENSE || c->n > kWarmMaxN) return false;
+    if (c->nr) return false;  // an nrhs context's buffers are not on warm_solve_kernels' restore list
     if (c->flags & (CGX_TIMING | CGX_PHASES | CGX_HOST_STREAM | CGX_SYMMETRIC)) return false;
     const char *e = std::getenv("CGX_WARM");
     return !(e && *e == '0');
@@ -619,6 +620,7 @@ extern "C" {
 int cgx_solve_begin(cgx_ctx *c) {
     const Range range_("cgx_solve_begin");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
+    if (c->nr) return nrhs_begin(c);
     return do_begin(c);
 }
 
@@ -711,7 +713,7 @@ int cgx_iterate(cgx_ctx *c, int64_t count, double eps, int64_t *done, int *conve
         return fail(CGX_ERR_STATE, "an earlier cgx_iterate failed part-way through iteration %lld: the solve "
                                    "cannot continue (cgx_solve_begin starts a new one)", (long long)c->k);
     TRY(check_x_complete(c));
-    const int rc = iterate_calls(c, count, eps, done, converged);
+    const int rc = c->nr ? nrhs_iterate(c, count, eps, done, converged) : iterate_calls(c, count, eps, done, converged);
     if (rc != CGX_OK) {
         // Part of an iteration may have run on some row blocks (or all of
         // r's update without x's): repeating it would apply it twice.  And
@@ -748,6 +750,7 @@ static int iterate_calls(cgx_ctx *c, int64_t count, double eps, int64_t *done, i
 int cgx_solve(cgx_ctx *c, void *x_inout, double eps, int64_t max_iter, cgx_stats *st) {
     const Range range_("cgx_solve");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
+    if (c->nr) return nrhs_solve(c, x_inout, eps, max_iter, st);
     if (x_inout) TRY(cgx_set_x(c, x_inout));
     TRY(sync_all(c));
     const auto t0 = std::chrono::steady_clock::now();
@@ -771,6 +774,7 @@ int cgx_solve(cgx_ctx *c, void *x_inout, double eps, int64_t max_iter, cgx_stats
 
 int cgx_get_stats(cgx_ctx *c, cgx_stats *st) {
     if (!c || !st) return fail(CGX_ERR_ARG, "NULL argument");
+    if (c->nr) return nrhs_get_stats(c, st);
     TRY(sync_all(c));
     TRY(timing_resolve(c));
     st->iterations = c->k;
@@ -831,6 +835,7 @@ void *cgx_stream(cgx_ctx *c) { return c ? (void *)c->sh[0].stream : nullptr; }
 
 int cgx_set_matvec_plan(cgx_ctx *c, int rows_per_wave, int chunks_in_flight, int nontemporal, int blocks_per_cu) {
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
+    if (c->nr) return nrhs_set_plan(c, rows_per_wave, chunks_in_flight, nontemporal, blocks_per_cu);
     if (f32ref(c) || c->op != OP_DENSE || (c->flags & CGX_SYMMETRIC))
         return fail(CGX_ERR_ARG, "only the fp64 row-major dense matVec has a tunable plan");
     const int R = rows_per_wave, U = chunks_in_flight;
@@ -869,7 +874,7 @@ int cgx_set_matvec_plan(cgx_ctx *c, int rows_per_wave, int chunks_in_flight, int
 
 int cgx_get_matvec_plan(cgx_ctx *c, int *rows_per_wave, int *chunks_in_flight, int *nontemporal, int *blocks) {
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
-    const MatvecPlan &pl = c->sh[0].plan;
+    const MatvecPlan &pl = c->nr ? c->nr->plan : c->sh[0].plan;
     if (rows_per_wave) *rows_per_wave = pl.R;
     if (chunks_in_flight) *chunks_in_flight = pl.U;
     if (nontemporal) *nontemporal = pl.nt;
@@ -880,6 +885,8 @@ int cgx_get_matvec_plan(cgx_ctx *c, int *rows_per_wave, int *chunks_in_flight, i
 int cgx_residual_norm(cgx_ctx *c, double *rnorm, double *bnorm) {
     const Range range_("cgx_residual_norm");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
+    if (c->nr)
+        return fail(CGX_ERR_ARG, "cgx_residual_norm: an nrhs context has one residual per system (cgx_residual_norms)");
     TRY(check_x_complete(c));
     // ||b - A x|| with the current x: allgather x, matVec, residual, two dots.
     TRY(settle_halo(c));

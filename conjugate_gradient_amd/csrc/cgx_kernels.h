@@ -73,6 +73,7 @@ struct MatvecPlan {
     int blocks = 0;   // grid (256-thread blocks), grid-stride over row groups
     int small = 0;    // > 0: k_matvec_small_f64 with this many threads per block (vector in LDS)
     int a32 = 0;      // 1: k_matvec_a32's plan (float A; U counts 256-column chunks, nt is 2 or 8)
+    int nrhs = 0;     // > 0: k_matvec_nrhs_f64's plan for this many vectors per pass (2, 4 or 8; nt is 2 or 8)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -118,6 +119,62 @@ MatvecPlan plan_matvec_a32(int device, int64_t rows, int R = 0, int U = 0, int n
 hipError_t matvec_a32(const MatvecPlan &pl, const float *A, int64_t lda, int64_t rows, int64_t cols, const double *v,
                       double *out, const double *pown, double *dot_out, const RedWs &ws, hipStream_t s,
                       const int64_t *gate = nullptr, int64_t *ts = nullptr);
+// ---- several right-hand sides per pass over A (cgx_matvec_nrhs.hip) -----------
+// Out[j*ldo + i] = sum_c A[i*lda + c] V[j*ldv + c] for j < nrhs: every element
+// of A loaded once and multiplied by K = nrhs_width(nrhs) vector elements (2,
+// 4 or 8; columns nrhs..K-1 re-read column 0 and are not stored).  Each
+// column's row sum adds in k_matvec_f64's order, so it is matvec_f64's result
+// on that column bit for bit under every plan.  pown != nullptr: also
+// dot_out[j] = pown[j*ldp ..] . Out[j*ldo ..] for every j < nrhs (fixed order).
+constexpr int kMaxNrhs = 8;
+inline int nrhs_width(int nrhs) { return nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
+// Reduction scratch of the nrhs kernels: kMaxNrhs * kMaxRedBlocks partials, kNrhsTickets counters.
+constexpr int kNrhsTickets = 4;
+enum NrhsTicket { TN_MATVEC = 0, TN_RESID = 1, TN_R = 2, TN_DOT = 3 };
+// The instantiated (K, R, U, policy): the policy is 2 (default-policy loads) or
+// 8 (non-temporal), both software-pipelined.
+bool matvec_nrhs_plan_ok(int K, int R, int U, int nt);
+// The plan for K vectors per pass: R/U/nt <= 0 / < 0 pick the defaults (env
+// CGX_MV_NRHS_PLAN="R=..,U=..,nt=..,bpc=.." may override with an instantiated plan).
+MatvecPlan plan_matvec_nrhs(int device, int64_t rows, int K, int R = 0, int U = 0, int nt = -1, int blocks_per_cu = 0,
+                            int64_t cols = 0);
+hipError_t matvec_nrhs_f64(const MatvecPlan &pl, const double *A, int64_t lda, int64_t rows, int64_t cols, int nrhs,
+                           const double *V, int64_t ldv, double *Out, int64_t ldo, const double *pown, int64_t ldp,
+                           double *dot_out, const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr,
+                           int64_t *ts = nullptr);
+// The scalars of an nrhs solve, on the device: r.r and p.Ap rings of 4 as the
+// one-system slots (cgx_ctx.h), per column; the true-residual dots; and the
+// per-column stopping record -- kdone[j] = k+1 and rrfinal[j] = r_j.r_j at the
+// iteration k that stopped column j (0: still iterating), alldone = k+1 of the
+// iteration that stopped the last column (the gate of every later launch).
+struct NrhsScal {
+    double rr[4][kMaxNrhs], pap[4][kMaxNrhs];
+    double tr[kMaxNrhs], tb[kMaxNrhs];
+    int64_t kdone[kMaxNrhs];
+    double rrfinal[kMaxNrhs];
+    int64_t alldone, pad_;
+};
+// The K-column vector kernels.  Column j of every vector starts at j*ld
+// doubles (ld even, bases 16-B aligned).  A column whose kdone is set is
+// frozen: no kernel writes its x, r, p or scalars again.
+// r_j = b_j - Ax_j (Ax == nullptr: b_j - 0.0); p_j = r_j when p != nullptr;
+// out[j] = r_j.r_j.  clear != nullptr: the stopping record of *clear and the
+// host-mapped word *hrec are reset (the start of a solve).
+hipError_t nrhs_residual_f64(int64_t n, int64_t ld, int nrhs, const double *b, const double *Ax, double *r, double *p,
+                             double *out, NrhsScal *clear, int64_t *hrec, const RedWs &ws, hipStream_t s);
+// out[j] = a_j . b_j
+hipError_t nrhs_dot_f64(int64_t n, int64_t ld, int nrhs, const double *a, const double *b, double *out,
+                        const RedWs &ws, hipStream_t s);
+// iteration k: r_j -= alpha_j Ap_j, sc->rr[ring(k+1)][j] = r_j.r_j, alpha_j = rr[ring(k)][j] / pap[ring(k)][j]
+hipError_t nrhs_update_r_f64(int64_t n, int64_t ld, int nrhs, int64_t k, double *r, const double *Ap, NrhsScal *sc,
+                             const RedWs &ws, hipStream_t s);
+// iteration k: x_j += alpha_j p_j; then the stopping decision per column
+// (eps >= 0: sqrt(r_j.r_j) < eps records kdone[j] = k+1, rrfinal[j], and, when
+// every column has stopped, alldone and the host-mapped hrec[0] = k+1); a
+// column that goes on gets p_j = r_j + beta_j p_j.
+hipError_t nrhs_update_xp_f64(int64_t n, int64_t ld, int nrhs, int64_t k, double eps, double *x, double *p,
+                              const double *r, NrhsScal *sc, int64_t *hrec, hipStream_t s);
+
 // r = b - Ax; p = r (if p); *rr_out = r.r (if rr_out).  Ax == nullptr: Ax = 0
 // (r = b - 0.0).  clear2: two int64 the kernel zeroes (the convergence record).
 hipError_t residual_f64(int64_t n, const double *b, const double *Ax, double *r, double *p,
@@ -294,13 +351,16 @@ hipError_t preload_poisson();
 hipError_t preload_ref_f32();
 hipError_t preload_symv();
 hipError_t preload_matvec_a32();
+hipError_t preload_matvec_nrhs();
 enum PreloadSet : unsigned {
-    PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32
+    PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
+    PL_MATVEC_NRHS = 64
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
-        {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32}};
+        {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
+        {PL_MATVEC_NRHS, preload_matvec_nrhs}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

@@ -25,6 +25,7 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
         else if (c->flags & CGX_SYMMETRIC) set |= PL_SYMV;
         else if (a32(c)) set |= PL_MATVEC_A32;
         else set |= PL_MATVEC;
+        if (c->nr) set |= PL_MATVEC_NRHS;
         HIPT(preload_kernels(set));
     }
     const size_t es = (size_t)c->es;
@@ -330,12 +331,14 @@ constexpr int64_t kFoldPMax = 2048;
 // matVec stages p in LDS (k_matvec_small_f64, every form of the iteration).
 bool small_matvec(const cgx_ctx *c) {
     if (c->mode != M_SINGLE || c->sh.size() != 1 || c->op != OP_DENSE || f32ref(c)) return false;
+    if (c->nr) return false;  // an nrhs context multiplies with k_matvec_nrhs_f64 only
     if (c->flags & (CGX_SYMMETRIC | CGX_HOST_STREAM | CGX_A_F32)) return false;  // not ported to float A
     return plan_matvec_small_f64(c->sh[0].dev, c->sh[0].nloc, c->lda).small > 0;
 }
 
 static bool can_fuse_p(const cgx_ctx *c) {
     if (c->mode != M_SINGLE || c->op != OP_DENSE || f32ref(c)) return false;
+    if (c->nr) return false;  // an nrhs context has an iteration of its own (cgx_nrhs.hip)
     if (c->flags & (CGX_SYMMETRIC | CGX_HOST_STREAM)) return false;
     if (c->n * 8 > INT32_MAX) return false;
     const char *e = std::getenv("CGX_FUSE_P");
@@ -400,6 +403,7 @@ int finish_create(cgx_ctx *c, cgx_ctx **out) {
     }
     auto undo = [c](int rc) {
         std::string keep = g_err;
+        nrhs_free(c);
         for (auto &t : c->sh) free_shard(t);
         delete c;
         snprintf(g_err, sizeof g_err, "%s", keep.c_str());
@@ -408,6 +412,10 @@ int finish_create(cgx_ctx *c, cgx_ctx **out) {
     for (auto &s : c->sh) {
         int rc = alloc_shard(c, s);
         if (rc == CGX_OK && (c->rot || c->halo_overlap) && &s == &c->sh.back()) rc = alloc_overlap(c);
+        if (rc != CGX_OK) return undo(rc);
+    }
+    if (c->nr) {  // the nrhs systems' vectors and scalars beside the shard's A
+        const int rc = nrhs_alloc(c, c->nr->nrhs);
         if (rc != CGX_OK) return undo(rc);
     }
     if (c->rot) {  // overlapped or plain exchange, by measurement (rank mode: a collective decision)
@@ -633,6 +641,33 @@ int cgx_create_multi(cgx_ctx **ctx, int64_t n, int nshards, const int *devices, 
     return create_multi(ctx, OP_DENSE, n, 0, nshards, devices, flags);
 }
 
+// nrhs systems on one matrix (cgx_nrhs.hip): a cgx_create context -- one GPU,
+// one resident row-major fp64 shard, A allocated and filled the same way --
+// whose vectors and scalars are NrhsState's.  The arguments are checked before
+// any device is touched.
+int cgx_create_nrhs(cgx_ctx **ctx, int64_t n, int nrhs, int device, int flags) {
+    if (!ctx) return fail(CGX_ERR_ARG, "cgx_create_nrhs: ctx is NULL");
+    *ctx = nullptr;
+    TRY(nrhs_check_args(nrhs, flags));
+    TRY(check_op(OP_DENSE, n, 0, 1, flags));
+    TRY(check_device(device));
+    cgx_ctx *c = new_ctx_op(OP_DENSE, n, 0, 1, flags);
+    if (!c) return fail(CGX_ERR_NOMEM, "host allocation failed");
+    c->nr = new (std::nothrow) NrhsState();
+    if (!c->nr) {
+        delete c;
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    c->nr->nrhs = nrhs;
+    c->mode = M_SINGLE;
+    c->sh.resize(1);
+    c->sh[0].dev = device;
+    c->sh[0].index = 0;
+    c->sh[0].row0 = 0;
+    c->sh[0].nloc = n;
+    return finish_create(c, ctx);
+}
+
 int cgx_get_unique_id(cgx_unique_id *id) {
     if (!id) return fail(CGX_ERR_ARG, "id is NULL");
     static_assert(sizeof(ncclUniqueId) == sizeof(cgx_unique_id), "unique id size");
@@ -673,6 +708,7 @@ int cgx_create_poisson_rank(cgx_ctx **ctx, int64_t m, int rank, int nranks, cons
 
 int cgx_fill(cgx_ctx *c, double b_value, double x_value) {
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
+    if (c->nr) return nrhs_fill(c, b_value, x_value);
     for (auto &s : c->sh) {
         TRY(set_dev(s));
         if (f32ref(c)) {
@@ -695,6 +731,7 @@ int cgx_destroy(cgx_ctx *ctx) {
     // aborted here instead of hanging in the stream syncs below
     const int rc = (ctx->mode == M_RCCL && !ctx->dead) ? sync_all(ctx) : CGX_OK;
     local_mt_stop(ctx);
+    nrhs_free(ctx);
     for (auto &s : ctx->sh) free_shard(s);
     delete ctx;
     return rc;
@@ -768,6 +805,10 @@ int cgx_set_rows(cgx_ctx *c, int64_t row0, int64_t nrows, const void *A_rows, in
     // A host-streamed A is rewritten in place on the host: first let every
     // copy (and kernel) still reading it from enqueued iterations finish.
     if (A_rows && (c->flags & CGX_HOST_STREAM)) TRY(sync_all(c));
+    if (c->nr) {  // nrhs blocks of nrows values each; A below as any context's
+        TRY(nrhs_set_vec_rows(c, row0, nrows, b_rows, x_rows));
+        b_rows = x_rows = nullptr;
+    }
     for (auto &s : c->sh) {
         const int64_t lo = std::max(row0, s.row0), hi = std::min(row0 + nrows, s.row0 + s.nloc);
         if (hi <= lo) continue;
@@ -897,6 +938,7 @@ int cgx_generate_spd(cgx_ctx *c, uint64_t seed) {
         HIPT(hipMemsetAsync(s.x, 0, s.nloc * c->es, s.stream));
         s.x_zero = true;
     }
+    if (c->nr) TRY(nrhs_generate_b(c, seed));  // b_j from seed + j, x0 = 0
     TRY(sync_all(c));
     c->state = ST_IDLE;
     return CGX_OK;
@@ -911,6 +953,7 @@ int cgx_get_x(cgx_ctx *c, void *x) {
     const Range range_("cgx_get_x");
     if (!c || !x) return fail(CGX_ERR_ARG, "NULL argument");
     TRY(check_x_complete(c));
+    if (c->nr) return nrhs_get_x(c, x);
     const size_t es = (size_t)c->es;
     if (c->mode == M_RCCL && c->nranks > 1) {
         Shard &s = c->sh[0];

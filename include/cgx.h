@@ -65,6 +65,35 @@
  *                  CGX_HOST_STREAM, CGX_PHASES, cgx_create_multi,
  *                  cgx_create_rank and the Poisson constructors.
  *
+ * Several right-hand sides (cgx_create_nrhs): nrhs systems A x_j = b_j on one
+ * matrix, solved together.  The reference runs conjugrad once per vectorb.txt
+ * and streams all of A on every iteration of every run; here one pass over A
+ * per iteration multiplies the p vectors of all nrhs systems.
+ *   - Batched CG, not block CG: the systems share only the read of A.  Each
+ *     has its own alpha, beta and stopping point, and each column's numerics
+ *     are those of a one-system CGX_F64 solve (row sums of A p_j bit for bit
+ *     cgx_matvec's; dots deterministic fixed-order sums per column).
+ *   - Stopping is per column, decided on the device: when sqrt(r_j.r_j) < eps
+ *     at iteration k, x_j gets that iteration's update, p_j is left (the
+ *     reference's break, serialConjugate.c:235-238), and column j is frozen:
+ *     no kernel writes x_j, r_j, p_j or its scalars again.  The solve ends
+ *     when every column has stopped (or at the count).
+ *   - Host layout: wherever a one-system context takes n values of b or x,
+ *     an nrhs context takes nrhs * n, system after system: b[j*n + i] is
+ *     entry i of system j (nrhs of the reference's vectors, one after the
+ *     other).  cgx_set_rows: b_rows / x_rows hold nrhs blocks of nrows values.
+ *   - cgx_generate_spd(seed): A as a one-system context's; b_j is the b that
+ *     seed + j gives (column 0 is the one-system context's system); x0 = 0.
+ *   - cgx_get_stats: iterations = the largest column count, converged = every
+ *     column converged, rr = the largest final r.r; cgx_get_stats_rhs gives
+ *     column j's.  cgx_residual_norm is CGX_ERR_ARG (cgx_residual_norms).
+ *   - cgx_set_matvec_plan accepts exactly the instantiated (rows per wave,
+ *     chunks in flight) of k_matvec_nrhs_f64 for the context's width (nrhs
+ *     rounded up to 2, 4 or 8): width 2: (2,4) (4,2) (4,4) (8,2); 4: (4,2)
+ *     (4,4) (8,2); 8: (4,1) (4,2); load policy 2 or 8.
+ *   - One GPU, CGX_F64, A resident row-major, optionally CGX_TIMING; every
+ *     other flag bit is CGX_ERR_ARG.  No creation warm-up.
+ *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
  * the p vector is allgathered and the two scalars p.Ap and r.r are
@@ -83,7 +112,9 @@ extern "C" {
 #endif
 
 #define CGX_VERSION 101 /* 0.1.1: cgx_overlap_info gained the end-to-end form times; CGX_A_F32 added (a new
-                           flag bit: no existing call changes meaning) */
+                           flag bit: no existing call changes meaning); cgx_create_nrhs and its
+                           entry points added (new functions only: no struct changes size, no
+                           existing call changes meaning, so the version stays) */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -372,6 +403,20 @@ int cgx_create_poisson_multi(cgx_ctx **ctx, int64_t m, int nshards, const int *d
 int cgx_create_poisson_rank(cgx_ctx **ctx, int64_t m, int rank, int nranks,
                             const cgx_unique_id *id, int device, int flags);
 
+#define CGX_MAX_NRHS 8
+/* One GPU, dense fp64, A resident row-major: nrhs (1..CGX_MAX_NRHS) systems
+ * A x_j = b_j solved together, one read of A per iteration (see "Several
+ * right-hand sides" above).  flags: CGX_F64, optionally with CGX_TIMING. */
+int cgx_create_nrhs(cgx_ctx **ctx, int64_t n, int nrhs, int device, int flags);
+int cgx_get_nrhs(const cgx_ctx *ctx, int *nrhs);          /* 1 for every other context */
+/* Column j's iterations, converged and rr of the last solve (the other
+ * fields as cgx_get_stats).  j = 0 on any other context: cgx_get_stats. */
+int cgx_get_stats_rhs(cgx_ctx *ctx, int j, cgx_stats *st);
+/* True residuals of the current x: rnorm[j] = ||b_j - A x_j||_2, bnorm[j] =
+ * ||b_j||_2, nrhs entries each; either may be NULL.  Overwrites r and p: ends
+ * a solve in progress.  (Any other context: one entry, cgx_residual_norm's.) */
+int cgx_residual_norms(cgx_ctx *ctx, double *rnorm, double *bnorm);
+
 int cgx_destroy(cgx_ctx *ctx);
 int cgx_get_info(const cgx_ctx *ctx, cgx_info *info);
 int cgx_get_comm_info(cgx_ctx *ctx, cgx_comm_info *info);
@@ -468,6 +513,11 @@ int cgx_dev_synchronize(void);
  * CGX_A_F32: A is float (lda in floats), v and out are double. */
 int cgx_matvec(int dtype, const void *A, int64_t lda, int64_t rows, int64_t cols,
                const void *v, void *out, void *stream);
+/* nrhs vectors per pass over A (fp64 only):
+ * Out[j*ldo + i] = sum_c A[i*lda + c] * V[j*ldv + c], j < nrhs (1..CGX_MAX_NRHS).
+ * Column j of Out is cgx_matvec(CGX_F64)'s result on column j of V bit for bit. */
+int cgx_matvec_nrhs(const void *A, int64_t lda, int64_t rows, int64_t cols, int nrhs,
+                    const void *V, int64_t ldv, void *Out, int64_t ldo, void *stream);
 /* vecVec: *out_dev = a . b */
 int cgx_dot(int dtype, int64_t n, const void *a, const void *b, void *out_dev, void *stream);
 /* residual x2 + vecVec: r = b - Ax; p = b - Ax; *rr_dev = r.r (rr_dev may be NULL) */

@@ -14,6 +14,13 @@ for iterations/s, and -- the correctness cross-check at the timed size -- a
 solve to 1e-10 under CGX_A_F32 with its true residual.
 
   python tools/sweep_matvec.py --a-fp32 [--n 65536] [--rounds 5] [--iters 4]
+
+--nrhs K: the instantiated plans of k_matvec_nrhs_f64 (cgx_create_nrhs, K
+right-hand sides per pass over A) in the same form: interleaved rounds, the
+k_matvec_f64 default plan in the same rounds, every plan's first launch
+recorded apart ("record": "first").
+
+  python tools/sweep_matvec.py --nrhs 4 [--n 65536] [--rounds 5] [--iters 4]
 """
 import argparse
 import itertools
@@ -96,6 +103,73 @@ def sweep_a32(args):
                           "residual_norm": rn, "b_norm": bn, "residual_below_stop": bool(rn < 1e-10 * bn)}), flush=True)
 
 
+NRHS_PLANS = {2: [(2, 4), (4, 2), (4, 4), (8, 2)], 4: [(4, 2), (4, 4), (8, 2)], 8: [(4, 1), (4, 2)]}
+
+
+def time_plan_first(s, plan, iters):
+    """(ms of the plan's first launch in this process, ms per launch of the `iters` after it)."""
+    if plan is not None:
+        s.set_matvec_plan(*plan)
+    s.reset_timing()
+    s.iterate(1, eps=-1.0)
+    first = s.stats()
+    first_ms = first.matvec_ms / first.matvec_count
+    s.reset_timing()
+    s.iterate(iters, eps=-1.0)
+    st = s.stats()
+    return first_ms, st.matvec_ms / st.matvec_count
+
+
+def sweep_nrhs(args):
+    """The instantiated plans of k_matvec_nrhs_f64 for nrhs = K, interleaved with the k_matvec_f64 default plan
+    in the same rounds on the same generated A.  GB/s on A's bytes plus the vectors each launch needs
+    (8 N^2 + 16 K N against 8 N^2 + 16 N).  Round 0's first launch of every plan goes to records of its own
+    ("record": "first"), not into the medians."""
+    n, K = args.n, args.nrhs
+    width = 2 if K <= 2 else 4 if K <= 4 else 8
+    s1 = cg.Solver(n, flags=cg.CGX_F64 | cg.CGX_TIMING)
+    sk = cg.Solver(n, flags=cg.CGX_F64 | cg.CGX_TIMING, nrhs=K)
+    for s in (s1, sk):
+        s.generate_spd(42)
+        s.begin()
+    nts = [int(v) for v in args.nt.split(",")] if args.nt != "0,1" else [2, 8]
+    configs = [(R, U, nt, 0) for (R, U) in NRHS_PLANS[width] for nt in nts]
+    times = {c: [] for c in configs}
+    times["f64"] = []
+    firsts = {}
+    plans = {"f64": s1.matvec_plan(), "default": sk.matvec_plan()}
+    for rnd in range(args.rounds):
+        f, t = time_plan_first(s1, None, args.iters)
+        times["f64"].append(t)
+        firsts.setdefault("f64", f)
+        for c in configs:
+            f, t = time_plan_first(sk, c, args.iters)
+            times[c].append(t)
+            firsts.setdefault(c, f)
+            plans[c] = sk.matvec_plan()
+    rows = []
+    for c, t in times.items():
+        k = 1 if c == "f64" else K
+        nbytes = 8 * n * n + 16 * k * n
+        med, mn, mx = statistics.median(t), min(t), max(t)
+        pl = plans[c]
+        rows.append({"record": "sweep", "kernel": "k_matvec_f64" if c == "f64" else "k_matvec_nrhs_f64", "n": n,
+                     "nrhs": k, "R": pl["R"], "U": pl["U"], "nt": pl["nt"], "blocks": pl["blocks"], "rounds": len(t),
+                     "ms_med": med, "ms_min": mn, "ms_max": mx, "bytes": nbytes, "gbps_med": nbytes / med / 1e6,
+                     "gbps_best": nbytes / mn / 1e6, "a_tbps_med": 8 * n * n / med / 1e9})
+    rows.sort(key=lambda r: r["ms_med"])
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    for c, f in firsts.items():
+        pl = plans[c]
+        print(json.dumps({"record": "first", "kernel": "k_matvec_f64" if c == "f64" else "k_matvec_nrhs_f64", "n": n,
+                          "nrhs": 1 if c == "f64" else K, "R": pl["R"], "U": pl["U"], "nt": pl["nt"], "ms": f}),
+              flush=True)
+    print(json.dumps({"record": "default_plan", "n": n, "nrhs": K, "plan": plans["default"]}), flush=True)
+    s1.close()
+    sk.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=65536)
@@ -106,9 +180,13 @@ def main():
     ap.add_argument("--nt", default="0,1")
     ap.add_argument("--bpc", default="0")
     ap.add_argument("--a-fp32", action="store_true", help="the CGX_A_F32 plans beside the CGX_F64 default")
+    ap.add_argument("--nrhs", type=int, default=0,
+                    help="K: the plans of k_matvec_nrhs_f64 for K right-hand sides beside the k_matvec_f64 default")
     args = ap.parse_args()
     if args.a_fp32:
         return sweep_a32(args)
+    if args.nrhs:
+        return sweep_nrhs(args)
     n = args.n
     s = cg.Solver(n, flags=cg.CGX_F64 | cg.CGX_TIMING)
     s.generate_spd(42)
