@@ -183,3 +183,176 @@ def test_matvec_f64_every_plan_bitwise_equal(monkeypatch, rows, cols):
         out = cg.DeviceArray(rows)
         cg.matVec(A_d, v_d, out, rows, cols)
         assert np.array_equal(out.to_host(), base), (R, U, nt)
+
+
+# ---- the fp64 BLAS-1 kernels at their edges ------------------------------------------------------
+# Reference: the same operation in np.longdouble.  a + s*b elementwise: |got - ref| <= 2^-52 (|a_i| + |s b_i|),
+# which covers the fused and the two-rounding evaluation; the scalar pairs (3/4, 5/8) have exact quotients.
+# Reductions: F64_TOL relative to sum|a_i b_i| (no term passes through more than ~64 additions here: a per-thread
+# chain, 6 wave steps, 4 waves, a partial chain of at most 8, the same again -- 7e-15).
+# Sizes: 2048 = one block's VEC span; 4196355 = 2048 * 2048 + 2051 takes the VEC grid-stride loop into a partial
+# second trip with an odd tail; 100001 wraps the scalar form's loop eight times.
+# Placement: every kernel has a VEC form (every pointer 16-byte aligned) and a scalar form; one operand 8 bytes
+# off the grid must select the scalar form for all of them.
+EDGE_N = [1, 2, 3, 255, 2047, 2048, 2049, 4097, 100001, 4196355]
+GUARD = 2  # sentinel elements on each side of a placed vector (16 bytes: the placement's phase is kept)
+SENTINEL = np.float64(-1.2345e300)
+EPS52 = 2.0 ** -52
+
+
+def ld(a):
+    return np.asarray(a, np.longdouble)
+
+
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+
+class Placed:
+    """A device vector `off` elements (0 or 1) past a 16-byte boundary, inside an array one element longer,
+    with sentinels before and after it; get() returns it after checking that every sentinel is untouched."""
+
+    def __init__(self, host, off):
+        host = np.atleast_1d(np.asarray(host, np.float64))
+        self.lo, self.hi = GUARD + off, GUARD + off + host.size
+        buf = np.full(GUARD + 1 + host.size + GUARD, SENTINEL)
+        buf[self.lo:self.hi] = host
+        self.d = dev(buf)
+        self.ptr = self.d.ptr + 8 * self.lo
+        assert (self.ptr % 16 == 0) == (off == 0)
+
+    def get(self):
+        buf = self.d.to_host()
+        out = np.concatenate([buf[:self.lo], buf[self.hi:]])
+        assert same_bits(out, np.full(out.size, SENTINEL)), "a guard element was written"
+        return buf[self.lo:self.hi]
+
+
+def placements(nops, n):
+    """(name, offsets): all aligned (VEC), all +8 (scalar), exactly one operand +8 (scalar for all) -- each
+    operand in turn at the small sizes, one of them at the large ones."""
+    yield "aligned", (0,) * nops
+    yield "all+8", (1,) * nops
+    for i in (range(nops) if n <= 5000 else [n % nops]):
+        yield f"only operand {i} +8", tuple(int(j == i) for j in range(nops))
+
+
+def call(name, *args):
+    """A CGX_F64 entry point on Placed vectors (kept alive here until the launch has finished), None or ints."""
+    L = cg.lib()
+    rc = getattr(L, name)(cg.CGX_F64, *(a.ptr if isinstance(a, Placed) else a for a in args), None)
+    assert rc == 0, (name, L.cgx_last_error())
+    assert L.cgx_dev_synchronize() == 0, (name, L.cgx_last_error())
+
+
+def sum_close(got, terms):
+    """got == sum(terms) to F64_TOL * sum|terms|, the sum taken in long double."""
+    t = ld(terms)
+    return abs(np.longdouble(got) - t.sum()) <= F64_TOL * np.abs(t).sum()
+
+
+@pytest.mark.parametrize("n", EDGE_N)
+def test_residual_f64_edges(n):
+    """cgx_residual(CGX_F64): r and p both written and equal, rr = r.r; rr_dev = NULL leaves r and p correct."""
+    rng = np.random.default_rng(n)
+    b, Ax = rng.random(n) - 0.5, rng.random(n) - 0.5
+    ref = ld(b) - ld(Ax)
+    bound = EPS52 * (np.abs(b) + np.abs(Ax))
+    for name, (ob, oa, orr, op) in placements(4, n):
+        runs = []
+        for with_rr in (True, True, False):
+            b_d, a_d = Placed(b, ob), Placed(Ax, oa)
+            r_d, p_d, rr_d = Placed(np.full(n, np.nan), orr), Placed(np.full(n, np.nan), op), Placed(np.nan, 0)
+            call("cgx_residual", n, b_d, a_d, r_d, p_d, rr_d if with_rr else None)
+            runs.append((r_d.get(), p_d.get(), rr_d.get()[0]))
+            assert same_bits(b_d.get(), b) and same_bits(a_d.get(), Ax), name
+        r, p, rr = runs[0]
+        assert same_bits(r, p) and np.all(np.abs(ld(r) - ref) <= bound), name
+        assert sum_close(rr, ld(r) * ld(r)), (name, rr)
+        assert same_bits(runs[1][0], r) and same_bits(runs[1][1], r) and runs[1][2] == rr, name  # deterministic
+        assert same_bits(runs[2][0], r) and same_bits(runs[2][1], r) and np.isnan(runs[2][2]), name
+
+
+@pytest.mark.parametrize("n", EDGE_N)
+def test_update_p_f64_edges(n):
+    """cgx_update_p(CGX_F64): p = r + (5/8) p elementwise; r untouched.  (Never called with CGX_F64 outside a
+    solve before; the odd-tail line of the VEC form is reached only here and in 4-iteration solves.)"""
+    rng = np.random.default_rng(n + 1)
+    p, r = rng.random(n) - 0.5, rng.random(n) - 0.5
+    beta = 0.625
+    ref = ld(r) + np.longdouble(beta) * ld(p)
+    bound = EPS52 * (np.abs(r) + np.abs(beta * p))
+    for name, (op, orr) in placements(2, n):
+        got = []
+        for _ in range(2):
+            p_d, r_d = Placed(p, op), Placed(r, orr)
+            call("cgx_update_p", n, p_d, r_d, Placed(5.0, 0), Placed(8.0, 0))
+            got.append(p_d.get())
+            assert same_bits(r_d.get(), r), name
+        assert np.all(np.abs(ld(got[0]) - ref) <= bound), (name, np.abs(ld(got[0]) - ref).max())
+        assert same_bits(got[0], got[1]), name
+
+
+@pytest.mark.parametrize("n", EDGE_N)
+def test_update_xr_f64_edges(n):
+    """cgx_update_xr(CGX_F64): x += (3/4) p, r -= (3/4) Ap, rr = r.r; p and Ap unchanged."""
+    rng = np.random.default_rng(n + 2)
+    x, r, p, Ap = (rng.random(n) - 0.5 for _ in range(4))
+    alpha = 0.75
+    x_ref, r_ref = ld(x) + np.longdouble(alpha) * ld(p), ld(r) - np.longdouble(alpha) * ld(Ap)
+    xb, rb = EPS52 * (np.abs(x) + np.abs(alpha * p)), EPS52 * (np.abs(r) + np.abs(alpha * Ap))
+    for name, (ox, orr, op, oa) in placements(4, n):
+        got = []
+        for _ in range(2):
+            x_d, r_d, p_d, a_d, rr_d = Placed(x, ox), Placed(r, orr), Placed(p, op), Placed(Ap, oa), Placed(np.nan, 0)
+            call("cgx_update_xr", n, x_d, r_d, p_d, a_d, Placed(3.0, 0), Placed(4.0, 0),
+                 rr_d)
+            got.append((x_d.get(), r_d.get(), rr_d.get()[0]))
+            assert same_bits(p_d.get(), p) and same_bits(a_d.get(), Ap), name
+        xg, rg, rr = got[0]
+        assert np.all(np.abs(ld(xg) - x_ref) <= xb) and np.all(np.abs(ld(rg) - r_ref) <= rb), name
+        assert sum_close(rr, ld(rg) * ld(rg)), (name, rr)
+        assert same_bits(got[1][0], xg) and same_bits(got[1][1], rg) and got[1][2] == rr, name
+
+
+@pytest.mark.parametrize("n", EDGE_N)
+def test_dot_f64_edges(n):
+    rng = np.random.default_rng(n + 3)
+    a, b = rng.random(n) - 0.5, rng.random(n) - 0.5
+    for name, (oa, ob) in placements(2, n):
+        got = []
+        for _ in range(2):
+            a_d, b_d, out = Placed(a, oa), Placed(b, ob), Placed(np.nan, 0)
+            call("cgx_dot", n, a_d, b_d, out)
+            got.append(out.get()[0])
+            assert same_bits(a_d.get(), a) and same_bits(b_d.get(), b), name
+        assert sum_close(got[0], ld(a) * ld(b)), (name, got[0])
+        assert got[0] == got[1], name
+
+
+@pytest.mark.parametrize("off", [0, 1])
+def test_cg_ratio_cases_f64(off):
+    """cg_ratio's three cases at the kernel level (include/cgx.h, "Iterations past exact convergence";
+    test_indefinite_breakdown_is_not_hidden sees the last through a whole solve): 0/0 and a subnormal numerator
+    over 0 give 0 -- x and r stay bit for bit; a normal numerator over 0 is the plain quotient, Inf."""
+    n = 257
+    rng = np.random.default_rng(257)
+    x, r, p, Ap = (rng.random(n) - 0.5 for _ in range(4))
+    p[[0, 100, 256]] = 0.0, -0.0, 0.0  # the odd tail among them
+    for rsold in (0.0, 5e-324):
+        x_d, r_d, rr_d = Placed(x, off), Placed(r, off), Placed(np.nan, 0)
+        call("cgx_update_xr", n, x_d, r_d, Placed(p, off), Placed(Ap, off), Placed(rsold, 0),
+             Placed(0.0, 0), rr_d)
+        assert same_bits(x_d.get(), x) and same_bits(r_d.get(), r), rsold
+        assert sum_close(rr_d.get()[0], ld(r) * ld(r)), rsold
+    x_d, r_d, rr_d = Placed(x, off), Placed(r, off), Placed(np.nan, 0)
+    call("cgx_update_xr", n, x_d, r_d, Placed(p, off), Placed(Ap, off), Placed(1.0, 0),
+         Placed(0.0, 0), rr_d)
+    xg = x_d.get()
+    assert not np.isfinite(xg).any()
+    assert np.array_equal(np.isnan(xg), p == 0.0)
+    live = p != 0.0
+    assert np.all(np.isinf(xg[live])) and np.array_equal(np.sign(xg[live]), np.sign(p[live]))
+    p_d = Placed(p, off)
+    call("cgx_update_p", n, p_d, Placed(r, off), Placed(0.0, 0), Placed(0.0, 0))
+    assert np.array_equal(p_d.get(), r)  # beta = 0: p == r

@@ -11,6 +11,7 @@ import pytest
 
 import conjugate_gradient_amd as cg
 import oracle
+import _long_systems as ls
 from _cases import case
 
 pytestmark = pytest.mark.gpu
@@ -159,3 +160,38 @@ def test_symmetric_host_streamed_with_resident_tiles(monkeypatch, resident_mb):
         assert ia == ib and np.array_equal(xa.view(np.uint8), xb.view(np.uint8))
     xo, so = oracle.cg_f64(A2, b2, np.zeros(n), eps=1e-10)
     assert out[resident_mb][1][1] == so.iterations and rel(out[resident_mb][1][0], xo) <= TOL
+
+
+def _probe_system(n):
+    """A signed, off-diagonal-heavy SPD matrix of tests/_long_systems.py and a seeded v in [-0.5, 0.5)."""
+    A = ls.system(*ls.SYSTEMS.get(n, (n, min(12, n), n)))[0]
+    return A, np.random.default_rng(n + 17).random(n) - 0.5
+
+
+PROBES = [(n, kind) for kind in ("resident", "dense") for n in (1, 5, 127, 128, 129, 300, 1000, 2304)] + \
+    [(1000, "streamed"), (2304, "streamed")]
+
+
+@pytest.mark.parametrize("n,kind", PROBES)
+def test_symmetric_matvec_elementwise(monkeypatch, n, kind):
+    """k_symv_f64 / k_symv_reduce_f64 row by row, one iteration as the probe of A v: with b = 0 and x0 = v,
+    x1 = v + alpha (-A v), alpha = (Av.Av) / (Av.A(Av)).  Against the np.longdouble evaluation,
+    |x1_i - ref_i| <= 1e-13 (|v_i| + |alpha| (|A||v|)_i): the project's reordered-sum bound per row (alpha's
+    own relative error, of order n 2^-53, is below it).  A row summed from a wrong or transposed tile moves
+    x1_i by many orders more.  Resident tiles, host-streamed tiles (1 MiB chunks), and the row-major CGX_F64
+    context as the control."""
+    monkeypatch.setenv("CGX_STREAM_TILE_MB", "1")
+    A, v = _probe_system(n)
+    flags = {"resident": SYM, "streamed": SYM | cg.CGX_HOST_STREAM, "dense": cg.CGX_F64}[kind]
+    with cg.Solver(n, flags=flags) as s:
+        s.set_system(A, np.zeros(n), v)
+        x1, st = s.solve(None, eps=-1.0, max_iter=1)
+    assert st.iterations == 1
+    Al, vl = A.astype(np.longdouble), v.astype(np.longdouble)
+    Av = Al @ vl
+    alpha = (Av @ Av) / (Av @ (Al @ Av))
+    ref = vl - alpha * Av
+    bound = 1e-13 * (np.abs(v) + abs(float(alpha)) * (np.abs(A) @ np.abs(v)))
+    err = np.abs(x1.astype(np.longdouble) - ref).astype(np.float64)
+    print(f"\n{kind} n={n}: worst |x1 - ref| / bound = {np.max(err / bound):.3g}")
+    assert np.all(err <= bound), (int(np.argmax(err / bound)), float(np.max(err / bound)))
