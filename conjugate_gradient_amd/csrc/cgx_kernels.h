@@ -86,6 +86,23 @@ MatvecPlan plan_matvec_f64(int device, int64_t rows, int R = 0, int U = 0, int n
 // otherwise.  CGX_MV_SMALL=0 turns it off; CGX_SMALL_PLAN="threads=..,U=..,nt=.."
 // picks the block size (512, 1024), chunks per step (4, 8) and A's load policy.
 MatvecPlan plan_matvec_small_f64(int device, int64_t rows, int64_t lda);
+// What the plans of the row-streaming family share (cgx_matvec.hip).
+// The grid of kernel fn with R rows per wave: its occupancy (per_cu_fallback
+// blocks per CU when the query fails), then env's "bpc", then blocks_per_cu
+// (> 0), times the CUs; at most the blocks the row groups need and kMaxRedBlocks.
+int plan_grid(const void *fn, int device, int64_t rows, int R, int per_cu_fallback, const char *env, int blocks_per_cu);
+// (R, U, nt) of a family whose plans are a list (ok(pl.nrhs, R, U, nt) says
+// whether one is instantiated): env's plan when it names one, then the
+// arguments (R, U > 0, nt >= 0), then (fallback_R, fallback_U, 8).
+void plan_listed(MatvecPlan &pl, const char *env, int R, int U, int nt, bool (*ok)(int K, int R, int U, int nt),
+                 int fallback_R, int fallback_U);
+// The columns that go through the vector path: the whole chunks of `chunk`
+// columns when no pointer has a bit of its alignment mask set (misaligned: the
+// OR of those bits) and the pitch keeps every row aligned; otherwise 0, every
+// column through the scalar tail.
+inline int64_t matvec_vec_cols(uintptr_t misaligned, bool pitch_ok, int64_t cols, int chunk) {
+    return (misaligned == 0 && pitch_ok) ? (cols & ~int64_t(chunk - 1)) : 0;
+}
 
 // ---- fp64 -------------------------------------------------------------------
 // out[i] = sum_j A[i*lda+j] v[j]; if pown != nullptr also *dot_out = pown . out

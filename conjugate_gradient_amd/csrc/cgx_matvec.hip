@@ -17,25 +17,18 @@
 // partials in fixed slots, summed in index order by the last block to arrive
 // (write-through sc1 partials and a relaxed ticket, the fence-free form of
 // cdna_hip_programming.md Guideline 16).
-#include "cgx_device.h"
+#include "cgx_matvec_core.h"
 
 #include <algorithm>
 
 namespace cgx {
 namespace {
 
-// Load policy of the A stream (the only data a matVec reads once):
-//   0 plain global_load, 1 global_load ... nt, 2 / 8 software-pipelined
-//   global_load, default policy / nt (8 = the default plan).  The variants measured and not
-//   adopted (buffer loads with other cache bits, a flattened pipeline,
-//   LDS-staged p, SGPR row bases) live in tools/microbench/matvec_variants.hip.
-//   All give the same row sums bit for bit.
-template <int POL>
-__device__ __forceinline__ d2 load_a(const d2 *p) {
-    if constexpr (POL == 1) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-
+// k_matvec_f64 keeps its own pipeline, walk and epilogue below: built from
+// cgx_matvec_core.h's pieces its default plan measured 0.4 % slower (4.777
+// against 4.758 ms per launch at 65536^2, profiles/matvec_core_ab.jsonl); only
+// the A load policy is shared.  The folded matVec further down is built from
+// the shared pieces.
 // ---------------------------------------------------------------------------
 // matVec (serialConjugate.c:109-120 / parallel_cg.c:172-184), fp64.
 // Wave w owns row groups g = w, w + waves, ...; a group is R consecutive rows.
@@ -293,33 +286,19 @@ __global__ __launch_bounds__(kNT) void k_matvec_f64(
 // single-block pass over p at the end of the iteration.
 // Loads of r and p_{k-1} for step c + U go out before the FMAs of step c,
 // like k_matvec_f64's pipeline; the combine waits until the FMA step.
-template <int R, int U, int NTA>
-__device__ __forceinline__ void fold_load_step(const d2 *const (&arow)[R], const d2 *r2, const d2 *q2, int64_t c,
-                                               d2 (&rv)[U], d2 (&qv)[U], d2 (&av)[R][U]) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        rv[u] = r2[(c + u) * 64];
-        qv[u] = q2[(c + u) * 64];
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int u = 0; u < U; ++u) av[r][u] = load_a<NTA>(arow[r] + (c + u) * 64);
-}
-
-template <int R, int U>
-__device__ __forceinline__ void fold_fma_step(const d2 (&rv)[U], const d2 (&qv)[U], const d2 (&av)[R][U], double beta,
-                                              d2 (&acc)[R]) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const d2 pv = rv[u] + beta * qv[u];  // p = r + beta p (k_update_xp_f64's expression)
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            acc[r].x = __builtin_fma(av[r][u].x, pv.x, acc[r].x);
-            acc[r].y = __builtin_fma(av[r][u].y, pv.y, acc[r].y);
-        }
-    }
-}
+// The vector operand p_k = r + beta p_{k-1} (k_update_xp_f64's expression):
+// r and p_{k-1} (q) are what a lane loads, the combine is the multiplier.
+struct VecFold {
+    struct Raw {
+        d2 r, q;
+    };
+    const double *rs, *qs;
+    const d2 *r, *q;  // at this lane
+    double beta;
+    __device__ __forceinline__ Raw load(int64_t c) const { return {r[c * 64], q[c * 64]}; }
+    __device__ __forceinline__ d2 get(const Raw &x) const { return x.r + beta * x.q; }
+    __device__ __forceinline__ double at(int64_t j) const { return rs[j] + beta * qs[j]; }
+};
 
 template <int R, int U, int NTA = 1>
 __global__ __launch_bounds__(kNT) void k_matvec_fold_f64(
@@ -331,69 +310,22 @@ __global__ __launch_bounds__(kNT) void k_matvec_fold_f64(
     ts_start(ts);
     const double beta = cg_ratio(*rr_new, *rr_old);
     const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int64_t ngroups = (rows + R - 1) / R;
-    const int64_t wstride = (int64_t)gridDim.x * (kNT / 64);
     const int64_t nchunk = vec_cols >> 7;
-    const d2 *r2 = reinterpret_cast<const d2 *>(r) + lane;
-    const d2 *q2 = reinterpret_cast<const d2 *>(pold) + lane;
+    const VecFold vec[1] = {
+        {r, pold, reinterpret_cast<const d2 *>(r) + lane, reinterpret_cast<const d2 *>(pold) + lane, beta}};
     double dacc = 0.0;
-    for (int64_t g = (int64_t)blockIdx.x * (kNT / 64) + wid; g < ngroups; g += wstride) {
-        const int64_t r0 = g * R;
-        int64_t ridx[R];
-        const d2 *arow[R];
-        d2 acc[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            ridx[q] = (r0 + q < rows) ? (r0 + q) : (rows - 1);
-            arow[q] = reinterpret_cast<const d2 *>(A + ridx[q] * lda) + lane;
-            acc[q] = (d2)(0.0);
-        }
-        {
-            d2 ra[U], qa[U], aa[R][U], rb[U], qb[U], ab[R][U];
-            int64_t c = 0;
-            if (c + U <= nchunk) fold_load_step<R, U, NTA>(arow, r2, q2, c, ra, qa, aa);
-            while (c + U <= nchunk) {
-                const bool more = c + 2 * U <= nchunk;
-                if (more) fold_load_step<R, U, NTA>(arow, r2, q2, c + U, rb, qb, ab);
-                fold_fma_step<R, U>(ra, qa, aa, beta, acc);
-                c += U;
-                if (!more) break;
-                const bool more2 = c + 2 * U <= nchunk;
-                if (more2) fold_load_step<R, U, NTA>(arow, r2, q2, c + U, ra, qa, aa);
-                fold_fma_step<R, U>(rb, qb, ab, beta, acc);
-                c += U;
-                if (!more2) break;
-            }
-            for (; c < nchunk; ++c) {
-                const d2 pv = r2[c * 64] + beta * q2[c * 64];
-#pragma unroll
-                for (int q = 0; q < R; ++q) {
-                    const d2 a = load_a<NTA>(arow[q] + c * 64);
-                    acc[q].x = __builtin_fma(a.x, pv.x, acc[q].x);
-                    acc[q].y = __builtin_fma(a.y, pv.y, acc[q].y);
-                }
-            }
-        }
-        for (int64_t j = (nchunk << 7) + lane; j < cols; j += 64) {  // columns past the last whole chunk
-            const double pj = r[j] + beta * pold[j];
-#pragma unroll
-            for (int q = 0; q < R; ++q) acc[q].x = __builtin_fma(A[ridx[q] * lda + j], pj, acc[q].x);
-        }
-        double mine = 0.0;
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const double sum = wave_sum(acc[q].x + acc[q].y);
-            if (lane == q) mine = sum;
-        }
+    for_row_groups<1, R, d2, d2>(A, lda, rows, [&](int64_t r0, const auto &ridx, const auto &arow, auto &acc) {
+        chunks_pipe<NTA, U>(arow, vec, 0, nchunk, acc);
+        tail_cols(A, lda, ridx, vec, lane, nchunk << 7, cols, acc);  // columns past the last whole chunk
+        const double mine = row_sums(acc[0], lane);
         if (lane < R && r0 + lane < rows) {
             const int64_t i = r0 + lane;
-            const double pi = r[i] + beta * pold[i];
+            const double pi = vec[0].at(i);
             pnew[i] = pi;
             out[i] = mine;
             dacc += pi * mine;
         }
-    }
+    });
     grid_sum_last_block(dacc, partials, ticket, dot_out);
     ts_end(ts);
 }
@@ -614,18 +546,32 @@ MatvecPlan plan_matvec_f64(int device, int64_t rows, int R, int U, int nt, int b
     if (pl.R != 1 && pl.R != 2 && pl.R != 4 && pl.R != 8) pl.R = 4;
     if (pl.U != 2 && pl.U != 4 && pl.U != 8) pl.U = 4;
     if (pl.nt != 0 && pl.nt != 1 && pl.nt != 2 && pl.nt != 8) pl.nt = 8;
-    int per_cu = 0;
-    const void *fn = reinterpret_cast<const void *>(pick_mv(pl.R, pl.U, pl.nt));
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kNT, 0) != hipSuccess || per_cu <= 0)
-        per_cu = 2;
-    per_cu = env_opt("CGX_MV_PLAN", "bpc", per_cu);
-    if (blocks_per_cu > 0) per_cu = blocks_per_cu;
-    const int64_t groups = (rows + pl.R - 1) / pl.R;
-    const int64_t need = (groups + (kNT / 64) - 1) / (kNT / 64);
-    int64_t cap = (int64_t)per_cu * cus;
-    if (cap > kMaxRedBlocks) cap = kMaxRedBlocks;
-    pl.blocks = (int)std::max<int64_t>(1, std::min(need, cap));
+    pl.blocks = plan_grid(reinterpret_cast<const void *>(pick_mv(pl.R, pl.U, pl.nt)), device, rows, pl.R, 2,
+                          "CGX_MV_PLAN", blocks_per_cu);
     return pl;
+}
+
+int plan_grid(const void *fn, int device, int64_t rows, int R, int per_cu_fallback, const char *env,
+              int blocks_per_cu) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kNT, 0) != hipSuccess || per_cu <= 0)
+        per_cu = per_cu_fallback;
+    per_cu = env_opt(env, "bpc", per_cu);
+    if (blocks_per_cu > 0) per_cu = blocks_per_cu;
+    const int64_t groups = (rows + R - 1) / R;
+    const int64_t need = (groups + (kNT / 64) - 1) / (kNT / 64);
+    const int64_t cap = std::min<int64_t>((int64_t)per_cu * cu_count(device), kMaxRedBlocks);
+    return (int)std::max<int64_t>(1, std::min(need, cap));
+}
+
+void plan_listed(MatvecPlan &pl, const char *env, int R, int U, int nt, bool (*ok)(int K, int R, int U, int nt),
+                 int fallback_R, int fallback_U) {
+    const int eR = env_opt(env, "R", pl.R), eU = env_opt(env, "U", pl.U), en = env_opt(env, "nt", pl.nt);
+    if (ok(pl.nrhs, eR, eU, en)) pl.R = eR, pl.U = eU, pl.nt = en;
+    if (R > 0) pl.R = R;
+    if (U > 0) pl.U = U;
+    if (nt >= 0) pl.nt = nt;
+    if (!ok(pl.nrhs, pl.R, pl.U, pl.nt)) pl.R = fallback_R, pl.U = fallback_U, pl.nt = 8;
 }
 
 MatvecPlan plan_matvec_small_f64(int device, int64_t rows, int64_t lda) {
@@ -672,9 +618,8 @@ hipError_t matvec_f64(const MatvecPlan &pl, const double *A, int64_t lda, int64_
     }
     // The vector path needs 16-B-aligned rows and p; otherwise every column
     // goes through the scalar tail loop.
-    const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
-                         (lda & 1) == 0;
-    const int64_t vec_cols = aligned ? (cols & ~int64_t(127)) : 0;
+    const int64_t vec_cols = matvec_vec_cols(
+        (reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(v)) & 15, (lda & 1) == 0, cols, 128);
     MvFn fn = pick_mv(pl.R, pl.U, pl.nt);
     hipLaunchKernelGGL(fn, dim3(pl.blocks), dim3(kNT), 0, s, A, lda, rows, cols, vec_cols, int64_t(0),
                        vec_cols >> 7, int64_t(0), 1, 0, v, out, pown, dot_out, ws.partials, ws.tickets + T_MATVEC,

@@ -15,39 +15,32 @@
 // and the host copies work on plain contiguous vectors, and a column is what
 // cgx_matvec takes.  (The interleaved layout has not been measured.)
 //
-// Structure (k_matvec_f64's): 16-B-per-lane coalesced loads, a
-// wave covers one 1-KiB, 128-column chunk of a row per instruction, R rows per
-// wave share the K vector chunks held in registers, U chunks per row in
-// flight, the loads of step c+U issued before the FMAs of step c (two register
-// sets), the grid sized by occupancy and grid-striding over row groups, a
-// scalar tail for columns [vec_cols, cols), gate and ts as k_matvec_f64's, and
-// the K fused dots pown_j . out_j through one last-block hand-off
+// The structure cgx_matvec_core.h describes, with K vectors of d2 chunks held
+// in registers beside the R rows; gate and ts as k_matvec_f64's, and the K
+// fused dots pown_j . out_j through one last-block hand-off
 // (grid_sum_last_block_n: own partial slots and result slot per column).
 //
-// Summation order (a contract): for every column j a lane adds its two columns
-// of every chunk in chunk order into two accumulators, the tail columns into
-// .x, then x + y, then the wave sum -- the non-rotated k_matvec_f64's order,
-// for every instantiated (K, R, U, policy).  Row sums are therefore the bits
-// of cgx_matvec(CGX_F64) on that column alone under every plan.
+// Summation order (a contract): every column j is summed in the non-rotated
+// k_matvec_f64's order, for every instantiated (K, R, U, policy).  Row sums
+// are therefore the bits of cgx_matvec(CGX_F64) on that column alone under
+// every plan.
 //
 // Registers per lane (32-bit VGPRs): accumulators 4 R K, one A set 4 R U, one
 // vector set 4 K U, two sets in the pipeline; 256 threads per block, one wave
 // per SIMD, so up to 512 (VGPR + AGPR).  No instantiated plan uses scratch
 // (DESIGN.md lists every instantiation's resource usage).
-#include "cgx_device.h"
+#include "cgx_matvec_core.h"
 
 #include <algorithm>
+#include <iterator>
 
 namespace cgx {
 namespace {
 
-// A load policy: 0 default-policy loads (plan policy 2), 1 non-temporal (8)
-template <int NT>
-__device__ __forceinline__ d2 nr_load_a(const d2 *p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-
+// k_matvec_nrhs_f64 keeps its own load / FMA steps, pipeline, walk and epilogue
+// (cgx_matvec_core.h's structure; only the A load policy is shared): built from
+// the shared pieces the K = 8 default at 65536^2, <8, 4, 1>, measured 1.2 %
+// slower per iteration (6.888 against 6.806 ms, profiles/matvec_core_ab.jsonl).
 template <int K, int R, int U, int NT>
 __device__ __forceinline__ void nr_load_step(const d2 *const (&arow)[R], const d2 *const (&v2)[K], int64_t c,
                                              d2 (&pv)[K][U], d2 (&av)[R][U]) {
@@ -58,7 +51,7 @@ __device__ __forceinline__ void nr_load_step(const d2 *const (&arow)[R], const d
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int u = 0; u < U; ++u) av[r][u] = nr_load_a<NT>(arow[r] + (c + u) * 64);
+        for (int u = 0; u < U; ++u) av[r][u] = load_a<NT>(arow[r] + (c + u) * 64);
 }
 
 template <int K, int R, int U>
@@ -99,7 +92,7 @@ __device__ __forceinline__ void nr_chunks_pipe(const d2 *const (&arow)[R], const
         for (int j = 0; j < K; ++j) pv[j] = v2[j][c * 64];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const d2 a = nr_load_a<NT>(arow[r] + c * 64);
+            const d2 a = load_a<NT>(arow[r] + c * 64);
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 acc[j][r].x = __builtin_fma(a.x, pv[j].x, acc[j][r].x);
@@ -197,21 +190,18 @@ constexpr NrPlan kNrPlans[] = {{2, 2, 4}, {2, 4, 2}, {2, 4, 4}, {2, 8, 2},  //
 // register sets beside them: R = 8, U = 1 compiles to 216 bytes of scratch per
 // lane, so it is not instantiated.)
 
-template <int NT>
+// the listed plan's kernel, or nullptr
+template <int NT, size_t I = 0>
 NrFn pick_nrhs_nt(int K, int R, int U) {
-    if (K == 2) {
-        if (R == 2) return k_matvec_nrhs_f64<2, 2, 4, NT>;
-        if (R == 4) return U == 2 ? k_matvec_nrhs_f64<2, 4, 2, NT> : k_matvec_nrhs_f64<2, 4, 4, NT>;
-        return k_matvec_nrhs_f64<2, 8, 2, NT>;
+    if constexpr (I == std::size(kNrPlans)) return nullptr;
+    else {
+        constexpr NrPlan p = kNrPlans[I];
+        return (p.K == K && p.R == R && p.U == U) ? k_matvec_nrhs_f64<p.K, p.R, p.U, NT>
+                                                  : pick_nrhs_nt<NT, I + 1>(K, R, U);
     }
-    if (K == 4) {
-        if (R == 4) return U == 2 ? k_matvec_nrhs_f64<4, 4, 2, NT> : k_matvec_nrhs_f64<4, 4, 4, NT>;
-        return k_matvec_nrhs_f64<4, 8, 2, NT>;
-    }
-    return U == 1 ? k_matvec_nrhs_f64<8, 4, 1, NT> : k_matvec_nrhs_f64<8, 4, 2, NT>;
 }
 NrFn pick_nrhs(int K, int R, int U, int nt) {
-    return nt == 8 ? pick_nrhs_nt<1>(K, R, U) : pick_nrhs_nt<0>(K, R, U);
+    return nt == 8 ? pick_nrhs_nt<1>(K, R, U) : nt == 2 ? pick_nrhs_nt<0>(K, R, U) : nullptr;
 }
 
 // ---------------------------------------------------------------------------
@@ -378,12 +368,7 @@ auto pick_k(int nrhs, F2 f2, F4 f4, F8 f8) {
 
 }  // namespace
 
-bool matvec_nrhs_plan_ok(int K, int R, int U, int nt) {
-    if (nt != 2 && nt != 8) return false;
-    for (const auto &p : kNrPlans)
-        if (p.K == K && p.R == R && p.U == U) return true;
-    return false;
-}
+bool matvec_nrhs_plan_ok(int K, int R, int U, int nt) { return pick_nrhs(K, R, U, nt) != nullptr; }
 
 MatvecPlan plan_matvec_nrhs(int device, int64_t rows, int K, int R, int U, int nt, int blocks_per_cu, int64_t cols) {
     MatvecPlan pl;
@@ -414,25 +399,11 @@ MatvecPlan plan_matvec_nrhs(int device, int64_t rows, int K, int R, int U, int n
     // an A of up to 64 MiB with default-policy loads, so it stays in the MALL
     // between iterations (as plan_matvec_f64)
     pl.nt = (cols > 0 && rows * cols * 8 <= (int64_t(64) << 20)) ? 2 : 8;
-    {  // CGX_MV_NRHS_PLAN="R=..,U=..,nt=..,bpc=..": taken when it names an instantiated plan
-        const int eR = env_opt("CGX_MV_NRHS_PLAN", "R", pl.R), eU = env_opt("CGX_MV_NRHS_PLAN", "U", pl.U),
-                  en = env_opt("CGX_MV_NRHS_PLAN", "nt", pl.nt);
-        if (matvec_nrhs_plan_ok(K, eR, eU, en)) pl.R = eR, pl.U = eU, pl.nt = en;
-    }
-    if (R > 0) pl.R = R;
-    if (U > 0) pl.U = U;
-    if (nt >= 0) pl.nt = nt;
-    if (!matvec_nrhs_plan_ok(K, pl.R, pl.U, pl.nt)) pl.R = 4, pl.U = 2, pl.nt = 8;  // instantiated for every K
-    int per_cu = 0;
-    const void *fn = reinterpret_cast<const void *>(pick_nrhs(K, pl.R, pl.U, pl.nt));
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kNT, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
-    per_cu = env_opt("CGX_MV_NRHS_PLAN", "bpc", per_cu);
-    if (blocks_per_cu > 0) per_cu = blocks_per_cu;
-    const int64_t groups = (rows + pl.R - 1) / pl.R;
-    const int64_t need = (groups + (kNT / 64) - 1) / (kNT / 64);
-    int64_t cap = (int64_t)per_cu * cus;
-    if (cap > kMaxRedBlocks) cap = kMaxRedBlocks;
-    pl.blocks = (int)std::max<int64_t>(1, std::min(need, cap));
+    // CGX_MV_NRHS_PLAN="R=..,U=..,nt=..,bpc=..": taken when it names an instantiated plan;
+    // the fallback R = 4, U = 2 is instantiated for every K
+    plan_listed(pl, "CGX_MV_NRHS_PLAN", R, U, nt, matvec_nrhs_plan_ok, 4, 2);
+    pl.blocks = plan_grid(reinterpret_cast<const void *>(pick_nrhs(K, pl.R, pl.U, pl.nt)), device, rows, pl.R, 1,
+                          "CGX_MV_NRHS_PLAN", blocks_per_cu);
     return pl;
 }
 
@@ -446,9 +417,9 @@ hipError_t matvec_nrhs_f64(const MatvecPlan &pl, const double *A, int64_t lda, i
     // The vector path needs 16-B-aligned rows and vectors (every column: an
     // even ldv when there is more than one); otherwise every column of A goes
     // through the scalar tail, as matvec_f64 decides for one vector.
-    const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(V)) & 15) == 0 &&
-                         (lda & 1) == 0 && (nrhs == 1 || (ldv & 1) == 0);
-    const int64_t vec_cols = aligned ? (cols & ~int64_t(127)) : 0;
+    const int64_t vec_cols =
+        matvec_vec_cols((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(V)) & 15,
+                        (lda & 1) == 0 && (nrhs == 1 || (ldv & 1) == 0), cols, 128);
     hipLaunchKernelGGL(pick_nrhs(pl.nrhs, pl.R, pl.U, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, A, lda, rows, cols,
                        vec_cols, nrhs, V, ldv, Out, ldo, pown, ldp, dot_out, ws.partials, ws.tickets + TN_MATVEC, gate,
                        ts);

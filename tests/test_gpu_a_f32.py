@@ -15,6 +15,7 @@ import pytest
 
 import conjugate_gradient_amd as cg
 import oracle
+import _matvec_order as mo
 from _cases import case
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +148,40 @@ def test_kernel_level_matvec_every_plan(monkeypatch, rows, cols, lda):
         o2 = cg.DeviceArray(rows, np.float64)
         cg.matVec(dA, dv, o2, rows, cols, lda)
         assert np.array_equal(o2.to_host(), y), (R, U, nt)
+
+
+# The order itself against its CPU statement (_matvec_order.py; shapes there), which the plan-against-plan
+# test above cannot see.  (cols, lda, v's offset in doubles from the 32-byte grid): a v 16 bytes off it or a
+# pitch that is no multiple of 4 floats sends every column through the scalar tail.
+ORDER_A32 = [(c, (c + 3) & ~3, 0) for c in mo.A32_COLS] + [(517, 520, 2), (517, 519, 0)]
+
+
+@pytest.mark.parametrize("plan", [None, "R=8,U=2,nt=8"])
+@pytest.mark.parametrize("cols,lda,voff", ORDER_A32)
+def test_kernel_level_matvec_is_the_documented_order(monkeypatch, cols, lda, voff, plan):
+    """k_matvec_a32's row sums are the CPU emulation of the documented order bit for bit: four accumulators
+    per lane over 256-column chunks, tail columns into .x, (x + y) + (z + w), the wave sum."""
+    if plan:
+        monkeypatch.setenv("CGX_MV_A32_PLAN", plan)
+    else:
+        monkeypatch.delenv("CGX_MV_A32_PLAN", raising=False)
+    A, v = mo.a32_case(cols, lda)
+    dA, dv, out = cg.DeviceArray.from_host(A), cg.DeviceArray.from_host(np.concatenate([np.zeros(voff), v])), \
+        cg.DeviceArray(mo.ROWS, np.float64)
+    L = cg.lib()
+    assert L.cgx_matvec(A_F32, dA.ptr, lda, mo.ROWS, cols, dv.ptr + 8 * voff, out.ptr, None) == 0, L.cgx_last_error()
+    assert L.cgx_dev_synchronize() == 0, L.cgx_last_error()
+    vec_cols = mo.vec_cols_a32(cols, dA.ptr, dv.ptr + 8 * voff, lda)
+    assert vec_cols == (cols & ~255 if voff == 0 and lda % 4 == 0 else 0)
+    want = np.array(order_a32(cols, lda, vec_cols))
+    got = out.to_host()
+    assert np.array_equal(got, want), np.flatnonzero(got != want)
+
+
+@functools.lru_cache(maxsize=None)
+def order_a32(cols, lda, vec_cols):
+    A, v = mo.a32_case(cols, lda)
+    return mo.matvec_a32(A, v, cols, vec_cols)
 
 
 def test_solver_plans_accepted_and_reported():

@@ -5,11 +5,14 @@ reference's operation order).  fp64 kernels are checked against the oracle's
 sequential fp64 loops with a stated tolerance: a reordered fp64 sum of n
 terms differs by at most ~n * 2^-53 * sum|a_i b_i|; we use 1e-13 relative to
 sum|a_i b_i| for n <= 8192 (bound 9e-13 worst case, ~1e-15 typical)."""
+import functools
+
 import numpy as np
 import pytest
 
 import conjugate_gradient_amd as cg
 import oracle
+import _matvec_order as mo
 
 pytestmark = pytest.mark.gpu
 
@@ -183,6 +186,62 @@ def test_matvec_f64_every_plan_bitwise_equal(monkeypatch, rows, cols):
         out = cg.DeviceArray(rows)
         cg.matVec(A_d, v_d, out, rows, cols)
         assert np.array_equal(out.to_host(), base), (R, U, nt)
+
+
+# The summation order itself, stated on the CPU (_matvec_order.py): the tests above compare plan with plan
+# and kernel with kernel, so a change of order in code they all share would pass them.  (cols, lda, v's
+# offset in doubles from the 16-byte grid); shapes: _matvec_order.py.  A v 8 bytes off the grid or an odd
+# pitch sends every column through the scalar tail -- so does lda = cols for an odd cols, and those sizes
+# run with the pitch rounded up to even as well: that is where their chunks, remainders and tails meet.
+ORDER_F64 = ([(c, c, 0) for c in mo.F64_COLS] + [(c, c + 1, 0) for c in mo.F64_COLS if c % 2] +
+             [(389, 389, 1), (389, 390, 1), (389, 391, 0)])
+
+
+@functools.lru_cache(maxsize=None)
+def order_f64(cols, lda, vector_path):
+    A, v = mo.f64_case(cols, lda)
+    return A, v, np.array(mo.matvec_f64(A, v, cols, cols & ~127 if vector_path else 0))
+
+
+def matvec_at(dtype, A, v, voff, cols, lda):
+    """Kernel-level cgx_matvec on A and on v placed voff doubles into a device array; (out, A's and v's address)."""
+    dA, dv, out = dev(A), dev(np.concatenate([np.zeros(voff), v])), cg.DeviceArray(mo.ROWS)
+    L = cg.lib()
+    assert L.cgx_matvec(dtype, dA.ptr, lda, mo.ROWS, cols, dv.ptr + 8 * voff, out.ptr, None) == 0, L.cgx_last_error()
+    assert L.cgx_dev_synchronize() == 0, L.cgx_last_error()
+    return out.to_host(), dA.ptr, dv.ptr + 8 * voff
+
+
+@pytest.mark.parametrize("plan", [None, "R=4,U=4,nt=8", "R=1,U=2,nt=0"])
+@pytest.mark.parametrize("cols,lda,voff", ORDER_F64)
+def test_matvec_f64_is_the_documented_order(monkeypatch, cols, lda, voff, plan):
+    """k_matvec_f64's row sums are the CPU emulation of the documented order bit for bit, under the default
+    plan, a four-rows-per-wave pipelined plan and an unpipelined one (the other plans: the every-plan test)."""
+    monkeypatch.delenv("CGX_MV_SMALL", raising=False)
+    if plan:
+        monkeypatch.setenv("CGX_MV_PLAN", plan)
+    else:
+        monkeypatch.delenv("CGX_MV_PLAN", raising=False)
+    A, v, want = order_f64(cols, lda, voff == 0 and lda % 2 == 0)
+    got, pa, pv = matvec_at(cg.CGX_F64, A, v, voff, cols, lda)
+    assert mo.vec_cols_f64(cols, pa, pv, lda) == (cols & ~127 if voff == 0 and lda % 2 == 0 else 0)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)
+
+
+@pytest.mark.parametrize("cols", [2048, 2560])
+def test_matvec_small_lds_is_the_documented_order(monkeypatch, cols):
+    """k_matvec_small_f64 (CGX_MV_SMALL=2 routes cgx_matvec through it) likewise: 16 chunks per row run with
+    U = 8, 20 with U = 4."""
+    monkeypatch.setenv("CGX_MV_SMALL", "2")
+    monkeypatch.delenv("CGX_SMALL_PLAN", raising=False)
+    monkeypatch.delenv("CGX_MV_PLAN", raising=False)
+    A, v, want = order_f64(cols, cols, True)
+    got, _, _ = matvec_at(cg.CGX_F64, A, v, 0, cols, cols)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)
+    # that the call above took the LDS-staged kernel: it refuses a v off the 16-byte grid on the host side,
+    # where k_matvec_f64 would send every column through its scalar tail and succeed
+    dA, dv, out = dev(A), dev(np.concatenate([np.zeros(1), v])), cg.DeviceArray(mo.ROWS)
+    assert cg.lib().cgx_matvec(cg.CGX_F64, dA.ptr, cols, mo.ROWS, cols, dv.ptr + 8, out.ptr, None) != 0
 
 
 # ---- the fp64 BLAS-1 kernels at their edges ------------------------------------------------------
