@@ -38,6 +38,7 @@ __all__ = [
     "Solver", "lib", "build",
     "device_pci_bus_id", "device_link",
     "CGX_MAX_NRHS", "matVec_nrhs",
+    "CGX_CSR_ACTIVE", "spmv_csr",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
     "count_text", "read_dims", "device_count", "get_unique_id", "DeviceArray",
 ]
@@ -64,6 +65,7 @@ CGX_FOLDED_ACTIVE = 0x800000
 CGX_HALO_PULL_ACTIVE = 0x1000000
 CGX_THREADS_ACTIVE = 0x2000000
 CGX_HALO_OVERLAP_ACTIVE = 0x4000000
+CGX_CSR_ACTIVE = 0x8000000  # reported in info.flags: a cgx_create_csr context (Solver(n, csr_nnz=...))
 CGX_MAX_NRHS = 8  # cgx_create_nrhs: systems solved together on one matrix
 
 # cgx_phase_times indices (include/cgx.h), in the order the phases tile an iteration
@@ -170,6 +172,10 @@ def lib() -> ctypes.CDLL:
         "cgx_get_stats_rhs": ([vp, i32, ctypes.POINTER(Stats)], i32),
         "cgx_residual_norms": ([vp, ctypes.POINTER(f64), ctypes.POINTER(f64)], i32),
         "cgx_matvec_nrhs": ([vp, i64, i64, i64, i32, vp, i64, vp, i64, vp], i32),
+        "cgx_csr_check": ([i64, i64, vp, vp], i32),
+        "cgx_create_csr": ([pctx, i64, i64, i32, i32], i32),
+        "cgx_set_csr": ([vp, vp, vp, vp], i32),
+        "cgx_spmv_csr": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_get_unique_id": ([ctypes.POINTER(UniqueId)], i32),
         "cgx_rccl_available": ([], i32),
         "cgx_create_rank": ([pctx, i64, i32, i32, ctypes.POINTER(UniqueId), i32, i32], i32),
@@ -392,6 +398,49 @@ def matVec_nrhs(A: DeviceArray, V: DeviceArray, Out: DeviceArray, rows: int, col
            "cgx_matvec_nrhs")
 
 
+def _csr_arrays(indptr, indices=None, data=None):
+    """(indptr int64, indices int32, data float64), contiguous; ``indptr`` may be
+    an object with ``.indptr / .indices / .data`` (no scipy needed)."""
+    if indices is None and data is None and hasattr(indptr, "indptr"):
+        indptr, indices, data = indptr.indptr, indptr.indices, indptr.data
+    _need(indices is not None and data is not None, "CSR: indptr, indices and data are needed")
+    rp = np.ascontiguousarray(indptr, np.int64)
+    ci = np.ascontiguousarray(indices, np.int32)
+    va = np.ascontiguousarray(data, np.float64)
+    _need(rp.ndim == 1 and ci.ndim == 1 and va.ndim == 1, "CSR: indptr, indices and data are one-dimensional")
+    _need(ci.size == va.size, f"CSR: {ci.size} indices but {va.size} values")
+    return rp, ci, va
+
+
+def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int, cols: int) -> None:
+    """out[i] = sum_e data[e] * v[indices[e]] over row i's entries, in stored
+    order (k_spmv_csr_f64; the plan from CGX_SPMV_PLAN).  The structure comes
+    as host arrays: it is checked (cgx_csr_check) and only then uploaded, so the
+    kernel never sees an index outside v."""
+    rp, ci, va = _csr_arrays(indptr, indices, data)
+    _need(rows >= 1 and cols >= 1, "spmv_csr: need rows, cols >= 1")
+    _need(rp.size == rows + 1, f"spmv_csr: indptr has {rp.size} entries, rows + 1 = {rows + 1} needed")
+    _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_csr: float64 only")
+    _fits([v], cols, "spmv_csr v")
+    _fits([out], rows, "spmv_csr out")
+    L = lib()
+    # cgx_csr_check takes a square structure: fewer rows than columns are
+    # padded with empty rows (the same last row pointer), so the columns are
+    # checked against cols; with more rows than columns they are checked here
+    nsq = max(rows, cols)
+    rp_sq = rp if nsq == rows else np.concatenate([rp, np.full(nsq - rows, rp[-1], np.int64)])
+    _check(L.cgx_csr_check(nsq, ci.size, _ptr(rp_sq), _ptr(ci)), "cgx_csr_check")
+    bad = np.flatnonzero(ci >= cols)
+    _need(bad.size == 0, f"spmv_csr: indices[{bad[0] if bad.size else 0}] outside [0, {cols})")
+    d_rp, d_ci, d_va = DeviceArray.from_host(rp), DeviceArray.from_host(ci), DeviceArray.from_host(va)
+    try:
+        _check(L.cgx_spmv_csr(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, v.ptr, out.ptr, None), "cgx_spmv_csr")
+        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
+    finally:
+        for d in (d_rp, d_ci, d_va):
+            d.free()
+
+
 def vecVec(a: DeviceArray, b: DeviceArray, out: DeviceArray, n: int | None = None) -> None:
     """serialConjugate.c:145-155: out[0] = a . b (device scalar)."""
     n = n if n is not None else a.count
@@ -442,11 +491,16 @@ class Solver:
     ``nrhs=K`` (1..CGX_MAX_NRHS; cgx_create_nrhs): K systems on one matrix solved
     together, one read of A per iteration.  b and x arrays then have shape
     ``(K, n)`` (also for K = 1), the vector arguments of ``set_rows`` shape
-    ``(K, nrows)``, and ``solve`` / ``get_x`` return ``(K, n)``."""
+    ``(K, nrows)``, and ``solve`` / ``get_x`` return ``(K, n)``.
+
+    ``csr_nnz=nnz`` (cgx_create_csr): a sparse A in CSR storage with room for
+    ``nnz`` entries, one GPU, fp64; the matrix goes in through :meth:`set_csr`
+    (or build the solver with :meth:`from_csr`), b and x through ``set_rows``
+    / ``set_x`` / ``fill``."""
 
     def __init__(self, n: int, *, flags: int = CGX_F64, device: int = 0, devices=None,
                  rank: int | None = None, nranks: int | None = None, unique_id: bytes | None = None,
-                 poisson_m: int | None = None, nrhs: int | None = None):
+                 poisson_m: int | None = None, nrhs: int | None = None, csr_nnz: int | None = None):
         """Dense n x n system, or (poisson_m=m) the matrix-free 5-point Poisson
         operator on an m x m grid (n must then be m*m or None)."""
         self.nrhs = None
@@ -455,6 +509,12 @@ class Solver:
                   "Solver: nrhs runs on one GPU (not with devices=, rank= or poisson_m=)")
             _need(isinstance(nrhs, (int, np.integer)) and 1 <= nrhs <= CGX_MAX_NRHS,
                   f"Solver: nrhs must be in [1, {CGX_MAX_NRHS}] (got {nrhs})")
+        self.csr_nnz = None
+        if csr_nnz is not None:  # checked before any C call
+            _need(devices is None and rank is None and poisson_m is None and nrhs is None,
+                  "Solver: csr_nnz runs on one GPU (not with devices=, rank=, poisson_m= or nrhs=)")
+            _need(isinstance(csr_nnz, (int, np.integer)) and csr_nnz >= 0,
+                  f"Solver: csr_nnz must be an integer >= 0 (got {csr_nnz})")
         L = lib()
         self.poisson_m = poisson_m
         if poisson_m is not None:
@@ -485,10 +545,36 @@ class Solver:
         elif nrhs is not None:
             rc = L.cgx_create_nrhs(ctypes.byref(h), self.n, int(nrhs), device, flags)
             self.nrhs = int(nrhs) if rc == 0 else None
+        elif csr_nnz is not None:
+            rc = L.cgx_create_csr(ctypes.byref(h), self.n, int(csr_nnz), device, flags)
+            self.csr_nnz = int(csr_nnz) if rc == 0 else None
         else:
             rc = L.cgx_create(ctypes.byref(h), self.n, device, flags)
-        _check(rc, "cgx_create_nrhs" if nrhs is not None else "cgx_create")
+        _check(rc, "cgx_create_nrhs" if nrhs is not None else "cgx_create_csr" if csr_nnz is not None else "cgx_create")
         self._h = h.value
+
+    @classmethod
+    def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64) -> "Solver":
+        """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)."""
+        rp, ci, va = _csr_arrays(indptr, indices, data)
+        _need(rp.size >= 2, "from_csr: indptr needs n + 1 >= 2 entries")
+        s = cls(rp.size - 1, flags=flags, device=device, csr_nnz=int(ci.size))
+        try:
+            s.set_csr(rp, ci, va)
+        except Exception:
+            s.close()
+            raise
+        return s
+
+    def set_csr(self, indptr, indices=None, data=None) -> None:
+        """cgx_set_csr: the matrix of a ``csr_nnz`` solver from host arrays (cast
+        to int64 / int32 / float64).  The structure is checked before anything is
+        uploaded: CgxError(-4) names the first offence and the earlier matrix stays."""
+        _need(getattr(self, "csr_nnz", None) is not None, "set_csr: the solver was not created with csr_nnz=")
+        rp, ci, va = _csr_arrays(indptr, indices, data)
+        _need(rp.size == self.n + 1, f"set_csr: indptr has {rp.size} entries, n + 1 = {self.n + 1} needed")
+        _need(ci.size <= self.csr_nnz, f"set_csr: {ci.size} entries, the solver has room for {self.csr_nnz}")
+        _check(lib().cgx_set_csr(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr")
 
     def _vshape(self, rows: int | None = None) -> tuple:
         """The shape of a b or x argument: (n,), or (nrhs, n) on an nrhs context."""

@@ -35,7 +35,11 @@
  * --nrhs K (one GPU, fp64: K systems on the one matrix solved together, one
  * read of A per iteration -- cgx_create_nrhs; vectorb and initialguess then
  * hold K*N values, system after system, --print-x prints K*N lines, --stats
- * adds one line per system, and --spd takes b_j from seed S + j).
+ * adds one line per system, and --spd takes b_j from seed S + j),
+ * --csr (one GPU, fp64: the dense text matrix is read as always, only its
+ * entries that are not +-0 are kept, compressed to CSR row block by row block
+ * as they are parsed, and the solve runs through a cgx_create_csr context;
+ * --stats adds "nnz: <count>").
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -116,8 +120,9 @@ static void usage(const char *prog) {
             "usage: %s [--gpus P [--p2p]] [--fp32-ref | --symmetric | --a-fp32] [--eps E] [--max-iter M] [--dims FILE] [--n N]\n"
             "          [--threads T] [--print-x] [--stats] matrixA vectorb initialguess\n"
             "       %s --spd N [--seed S] [--gpus P] [--a-fp32] [--eps E] [--max-iter M] [--stats]\n"
-            "       %s --nrhs K ... (one GPU, fp64: K systems on one matrix; vectorb and initialguess hold K*N values)\n",
-            prog, prog, prog);
+            "       %s --nrhs K ... (one GPU, fp64: K systems on one matrix; vectorb and initialguess hold K*N values)\n"
+            "       %s --csr ... (one GPU, fp64: the matrix's non-zero entries only, solved as a sparse CSR system)\n",
+            prog, prog, prog, prog);
 }
 
 static int die_cgx(int rc, const char *what) {
@@ -146,6 +151,8 @@ typedef struct {
     int nrhs;  /* > 0: cgx_create_nrhs */
     cgx_ctx *ctx;
     double t_rt, t_done;  /* when the HIP runtime was up / creation finished (now_s) */
+    int csr;              /* --csr: cgx_create_csr, once the parse has counted the entries */
+    int64_t csr_nnz;      /* < 0: not counted yet (the thread only starts the HIP runtime) */
 } create_job;
 
 static void *create_ctx(void *arg) {
@@ -153,7 +160,9 @@ static void *create_ctx(void *arg) {
     int ndev0 = 0;
     cgx_device_count(&ndev0); /* starts the HIP runtime */
     j->t_rt = now_s();
-    if (j->nrhs > 0) {
+    if (j->csr) {
+        if (j->csr_nnz >= 0) j->rc = cgx_create_csr(&j->ctx, j->n, j->csr_nnz, 0, j->flags);
+    } else if (j->nrhs > 0) {
         j->rc = cgx_create_nrhs(&j->ctx, j->n, j->nrhs, 0, j->flags);
     } else if (j->gpus == 1) {
         j->rc = cgx_create(&j->ctx, j->n, 0, j->flags);
@@ -250,6 +259,51 @@ static int stream_parse(a_stream *st) {
     return 0;
 }
 
+/* --csr: A's text parsed row block by row block (the streaming reader's
+ * blocks) into one block buffer, and each block's entries that are not +-0
+ * appended to the CSR arrays, which grow as needed.  Returns 0, or the text
+ * reader's error (-2 short, -3 malformed), or -9 when memory runs out. */
+typedef struct {
+    int64_t *row_ptr;
+    int32_t *col_idx;
+    double *values;
+    int64_t nnz, cap;
+} csr_host;
+
+static int csr_parse(cgx_text *text, int64_t n, int64_t block_rows, double *blk, int threads, csr_host *m) {
+    m->row_ptr = malloc((size_t)(n + 1) * sizeof(int64_t));
+    m->cap = 8 * n > 1024 ? 8 * n : 1024;
+    m->col_idx = malloc((size_t)m->cap * sizeof(int32_t));
+    m->values = malloc((size_t)m->cap * sizeof(double));
+    m->nnz = 0;
+    if (!m->row_ptr || !m->col_idx || !m->values) return -9;
+    m->row_ptr[0] = 0;
+    for (int64_t row0 = 0; row0 < n; row0 += block_rows) {
+        const int64_t rows = row0 + block_rows <= n ? block_rows : n - row0;
+        const int rc = cgx_text_read_range(text, row0 * n, rows * n, 0, blk, threads);
+        if (rc != 0) return rc;
+        for (int64_t i = 0; i < rows; ++i) {
+            const double *row = blk + (size_t)i * (size_t)n;
+            if (m->nnz + n > m->cap) { /* room for a full row */
+                const int64_t cap = 2 * m->cap > m->nnz + n ? 2 * m->cap : m->nnz + n;
+                int32_t *ci = realloc(m->col_idx, (size_t)cap * sizeof(int32_t));
+                if (ci) m->col_idx = ci;
+                double *va = realloc(m->values, (size_t)cap * sizeof(double));
+                if (va) m->values = va;
+                if (!ci || !va) return -9;
+                m->cap = cap;
+            }
+            for (int64_t j = 0; j < n; ++j)
+                if (row[j] != 0.0) { /* +0 and -0 are dropped; everything else is an entry */
+                    m->col_idx[m->nnz] = (int32_t)j;
+                    m->values[m->nnz++] = row[j];
+                }
+            m->row_ptr[row0 + i + 1] = m->nnz;
+        }
+    }
+    return 0;
+}
+
 /* Whole-string numeric option values: "--eps abc" or "--gpus 2x" is an
  * error (exit 2), not a silent 0. */
 static int opt_ll(const char *name, const char *v, long long *out) {
@@ -271,7 +325,7 @@ static int opt_double(const char *name, const char *v, double *out) {
 
 int main(int argc, char **argv) {
     const double t_prog0 = now_s();
-    int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0, a_fp32 = 0;
+    int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0, a_fp32 = 0, csr = 0;
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
@@ -292,6 +346,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "--symmetric")) symmetric = 1;
         else if (!strcmp(a, "--a-fp32")) a_fp32 = 1;
         else if (!strcmp(a, "--p2p")) p2p = 1;
+        else if (!strcmp(a, "--csr")) csr = 1;
         else if (!strcmp(a, "--eps") && has_val) {
             if (!opt_double(a, argv[++i], &eps)) return 2;
         } else if (!strcmp(a, "--max-iter") && has_val) {
@@ -340,6 +395,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--nrhs is fp64 on one GPU with A resident (no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p)\n");
         return 2;
     }
+    if (csr && (fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
+        fprintf(stderr, "--csr is fp64 on one GPU from a matrix file (no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
+        return 2;
+    }
     const int64_t nsys = nrhs > 0 ? nrhs : 1; /* systems: vectors of nsys * n values */
 
     /* ---- N ---------------------------------------------------------------- */
@@ -359,6 +418,7 @@ int main(int argc, char **argv) {
         n /= nsys;
     }
     if (n < 1) { fprintf(stderr, "empty system\n"); return 1; }
+    if (csr && n > INT32_MAX) { fprintf(stderr, "--csr: n must be below 2^31\n"); return 1; }
     if (n % gpus != 0) { printf("%lld is not divisible by %d\n", (long long)n, gpus); return 1; } /* parallel_cg.c:88 */
 
     printf("Computing cg of matrix size : %lld\n", (long long)n * (long long)n); /* serialConjugate.c:58 */
@@ -393,11 +453,11 @@ int main(int argc, char **argv) {
     const char *re = getenv("CGX_CLI_RELEASE");
     const int defer_release = !(re && !strcmp(re, "during"));
     const char *se = getenv("CGX_CLI_STREAM");
-    const int stream_a = spd_n <= 0 && !(se && !strcmp(se, "0"));
+    const int stream_a = !csr && spd_n <= 0 && !(se && !strcmp(se, "0"));
     if (!x) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     if (spd_n > 0) {
         memset(x, 0, vlen * es);
-    } else if (stream_a) {
+    } else if (stream_a || csr) {
         b = malloc(vlen * es);
         if (!b) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     } else {
@@ -407,14 +467,58 @@ int main(int argc, char **argv) {
         b = malloc(vlen * es);
         if (!A || !b) { fprintf(stderr, "can't allocate memory for vector\n"); return 1; }
     }
-    create_job job = {n, gpus, flags, CGX_OK, (int)nrhs, NULL, 0.0, 0.0};
+    create_job job = {n, gpus, flags, CGX_OK, (int)nrhs, NULL, 0.0, 0.0, csr, -1};
+    csr_host csrm = {NULL, NULL, NULL, 0, 0};
     const double t_start = now_s();
     pthread_t creator;
     const int threaded = pthread_create(&creator, NULL, create_ctx, &job) == 0;
     if (!threaded) create_ctx(&job);
     int read_rc = 0, stream_rc = CGX_OK;
     double t_parsed = 0.0, t_h2d = 0.0;
-    if (stream_a) {
+    if (csr) {
+        /* A: indexed once, then parsed and compressed row block by row block
+         * while the helper thread starts the HIP runtime; the context is
+         * created once the entries are counted */
+        cgx_text *text = NULL;
+        const int orc = cgx_text_open(pos[0], threads, &text);
+        int stopped = 0;
+        const int64_t have = orc == 0 ? cgx_text_available(text, &stopped) : -1;
+        if (orc != 0) {
+            printf("Could not open file\n"); /* serialConjugate.c:103 */
+            fprintf(stderr, "%s: cannot open\n", pos[0]);
+            read_rc = -1;
+        } else if (have < n * n) {
+            fprintf(stderr, stopped ? "%s: malformed number\n" : "%s: fewer than %lld numbers\n", pos[0],
+                    (long long)(n * n));
+            read_rc = stopped ? -3 : -2;
+        }
+        if (!read_rc) {
+            const char *bm = getenv("CGX_CLI_BLOCK_MB");
+            const size_t row_bytes = (size_t)n * 8;
+            const size_t block_bytes = (size_t)(((bm && atof(bm) > 0) ? atof(bm) : 128.0) * 1048576.0);
+            int64_t block_rows = (int64_t)(block_bytes / row_bytes) > 0 ? (int64_t)(block_bytes / row_bytes) : 1;
+            if (block_rows > n) block_rows = n;
+            if (big_alloc(&Abuf, (size_t)block_rows * row_bytes) != 0) {
+                fprintf(stderr, "can't allocate memory for vector\n");
+                return 1;
+            }
+            const int prc = csr_parse(text, n, block_rows, (double *)Abuf.p, threads, &csrm);
+            if (prc == -9) fprintf(stderr, "can't allocate memory for vector\n");
+            else if (prc) fprintf(stderr, prc == -2 ? "%s: fewer than %lld numbers\n" : "%s: malformed number\n", pos[0],
+                                  (long long)(n * n));
+            read_rc = prc;
+            rel.buf = Abuf;
+        }
+        t_parsed = now_s();
+        if (threaded) pthread_join(creator, NULL); /* before any exit: HIP may be starting up on it */
+        if (!read_rc)
+            read_rc = read_file(pos[1], (int64_t)vlen, 0, b, threads) || read_file(pos[2], (int64_t)vlen, 0, x, 1);
+        rel.text = text;
+        if (!read_rc) {
+            job.csr_nnz = csrm.nnz;
+            create_ctx(&job);
+        }
+    } else if (stream_a) {
         /* A: indexed once, then parsed and sent row block by row block */
         a_stream st;
         memset(&st, 0, sizeof st);
@@ -509,6 +613,16 @@ int main(int argc, char **argv) {
         rc = cgx_generate_spd(ctx, seed);
         t_dist1 = now_s();
         if (rc != CGX_OK) return die_cgx(rc, "cgx_generate_spd");
+    } else if (csr) {
+        rc = cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, csrm.values);
+        if (rc != CGX_OK) return die_cgx(rc, "cgx_set_csr");
+        rc = cgx_set_rows(ctx, 0, n, NULL, n, b, x);
+        t_dist1 = now_s();
+        free(b);
+        free(csrm.row_ptr);
+        free(csrm.col_idx);
+        free(csrm.values);
+        if (rc != CGX_OK) return die_cgx(rc, "cgx_set_rows");
     } else if (stream_a) {
         /* A is on the device; b and x0 (MPI_Bcast / MPI_Scatter of the vectors) */
         rc = cgx_set_rows(ctx, 0, n, NULL, n, b, x);
@@ -554,6 +668,7 @@ int main(int argc, char **argv) {
     if (stats)
         printf("iterations: %lld converged: %d residual_norm: %.6e\n", (long long)st.iterations, st.converged,
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
+    if (stats && csr) printf("nnz: %lld\n", (long long)csrm.nnz);
     if (stats && nrhs > 0)
         for (int j = 0; j < (int)nrhs; ++j) {
             cgx_stats sj;

@@ -1,0 +1,97 @@
+// cgx_csr.hip -- cgx_create_csr contexts (cgx_ctx.h, OP_CSR): a general sparse
+// A in CSR storage on one GPU, fp64.  The context is a cgx_create context
+// without the dense A: its vectors, scalars, stream, events and iteration are
+// the same, and launch_matvec multiplies with k_spmv_csr_f64 (cgx_spmv.hip).
+//
+// The kernel reads v[col_idx[e]] unchecked, so the structure is checked on the
+// host (cgx_csr_check) before anything is uploaded: no path of a context
+// reaches the kernel with indices that did not pass.
+#include "cgx_ctx.h"
+
+namespace cgxh {
+
+int csr_need_matrix(const cgx_ctx *c, const char *what) {
+    if (c->op == OP_CSR && c->csr_nnz < 0)
+        return fail(CGX_ERR_STATE, "%s: no matrix yet (cgx_set_csr comes first on a cgx_create_csr context)", what);
+    return CGX_OK;
+}
+
+int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
+    const bool r_ok = R == 1 || R == 2 || R == 4 || R == 8 || R == 16 || R == 32;
+    if (!r_ok || U != 1 || !spmv_csr_plan_ok(64 / R, nt))
+        return fail(CGX_ERR_ARG, "cgx_create_csr context: rows_per_wave (64 / T) must be 1, 2, 4, 8, 16 or 32, "
+                                 "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
+    Shard &s = c->sh[0];
+    TRY(set_dev(s));
+    s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu);
+    c->csr_plan_user = true;
+    return CGX_OK;
+}
+
+}  // namespace cgxh
+
+extern "C" {
+
+int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col_idx) {
+    if (n < 1 || nnz < 0) return fail(CGX_ERR_ARG, "cgx_csr_check: n must be >= 1 and nnz >= 0");
+    if (!row_ptr || (nnz > 0 && !col_idx)) return fail(CGX_ERR_ARG, "cgx_csr_check: NULL pointer");
+    if (row_ptr[0] != 0)
+        return fail(CGX_ERR_SHAPE, "cgx_csr_check: row_ptr[0] = %lld, must be 0", (long long)row_ptr[0]);
+    for (int64_t i = 0; i < n; ++i)
+        if (row_ptr[i + 1] < row_ptr[i])
+            return fail(CGX_ERR_SHAPE, "cgx_csr_check: row_ptr decreases at row %lld (%lld -> %lld)", (long long)i,
+                        (long long)row_ptr[i], (long long)row_ptr[i + 1]);
+    if (row_ptr[n] != nnz)
+        return fail(CGX_ERR_SHAPE, "cgx_csr_check: row_ptr[n] = %lld, must be nnz = %lld", (long long)row_ptr[n],
+                    (long long)nnz);
+    for (int64_t e = 0; e < nnz; ++e)
+        if (col_idx[e] < 0 || (int64_t)col_idx[e] >= n)
+            return fail(CGX_ERR_SHAPE, "cgx_csr_check: col_idx[%lld] = %d outside [0, %lld)", (long long)e,
+                        (int)col_idx[e], (long long)n);
+    return CGX_OK;
+}
+
+int cgx_set_csr(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, const double *values) {
+    const Range range_("cgx_set_csr");
+    if (!c) return fail(CGX_ERR_ARG, "cgx_set_csr: ctx is NULL");
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_csr: not a cgx_create_csr context");
+    if (!row_ptr) return fail(CGX_ERR_ARG, "cgx_set_csr: row_ptr is NULL");
+    const int64_t nnz = row_ptr[c->n];  // the entry count a valid row_ptr states; the check below tests the rest
+    if (nnz < 0) return fail(CGX_ERR_SHAPE, "cgx_set_csr: row_ptr[n] = %lld is negative", (long long)nnz);
+    if (nnz > c->csr_cap)
+        return fail(CGX_ERR_SHAPE, "cgx_set_csr: %lld entries, the context has room for %lld", (long long)nnz,
+                    (long long)c->csr_cap);
+    if (nnz > 0 && (!col_idx || !values)) return fail(CGX_ERR_ARG, "cgx_set_csr: col_idx / values is NULL");
+    TRY(cgx_csr_check(c->n, nnz, row_ptr, col_idx));  // nothing is uploaded when it fails
+    Shard &s = c->sh[0];
+    TRY(sync_all(c));  // iterations still enqueued read the arrays
+    TRY(set_dev(s));
+    HIPT(hipMemcpyAsync(s.csr_rp, row_ptr, (size_t)(c->n + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    if (nnz > 0) {
+        HIPT(hipMemcpyAsync(s.csr_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, s.stream));
+        HIPT(hipMemcpyAsync(s.csr_val, values, (size_t)nnz * 8, hipMemcpyHostToDevice, s.stream));
+    }
+    HIPT(hipStreamSynchronize(s.stream));
+    c->csr_nnz = nnz;
+    if (!c->csr_plan_user) s.plan = plan_spmv_csr(s.dev, s.nloc, nnz);
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
+int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const void *values,
+                 const void *v, void *out, void *stream) {
+    if (rows < 0 || cols < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_csr: bad shape");
+    if (!row_ptr || !col_idx || !values || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_csr: NULL pointer");
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    RedWs ws;
+    TRY(dev_ws(&ws));
+    // the entry count lives on the device: T comes from CGX_SPMV_PLAN or, without it, is 8
+    const MatvecPlan pl = plan_spmv_csr(dev, rows, /*nnz=*/-1);
+    HIPT(spmv_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
+                      static_cast<const double *>(values), rows, static_cast<const double *>(v),
+                      static_cast<double *>(out), nullptr, nullptr, ws, static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
+}  // extern "C"

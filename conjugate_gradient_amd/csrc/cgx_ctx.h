@@ -4,6 +4,7 @@
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
 //   cgx_nrhs.hip      cgx_create_nrhs contexts: several systems per pass over A
+//   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload)
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
 //
@@ -158,7 +159,7 @@ constexpr int kLookRing = 8;                    // pinned slots for the host's l
 inline int ring(int64_t j) { return (int)(j & 3); }
 
 enum Mode { M_SINGLE = 0, M_LOCAL = 1, M_RCCL = 2 };
-enum Op { OP_DENSE = 0, OP_POISSON = 1 };
+enum Op { OP_DENSE = 0, OP_POISSON = 1, OP_CSR = 2 };
 enum State { ST_IDLE = 0, ST_BEGUN = 1, ST_CONVERGED = 2 };
 
 constexpr int kEvPairs = 256;
@@ -180,7 +181,9 @@ struct Shard {
     ncclComm_t comm = nullptr;
     char *A = nullptr, *b = nullptr, *x = nullptr, *r = nullptr, *Ap = nullptr, *pfull = nullptr,
          *xfull = nullptr, *scal = nullptr;
-    char *pown = nullptr;  // this shard's p: pfull + row0 (dense) or the slab interior (Poisson)
+    char *pown = nullptr;  // this shard's p: pfull + row0 (dense, CSR) or the slab interior (Poisson)
+    // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap]); no s.A
+    char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
     // fused Poisson iteration: r with halo rows (r = rh + one row) and a
     // second p slab; p_k lives in pfull for even k, in p2 for odd k
     char *rh = nullptr, *p2 = nullptr;
@@ -271,7 +274,12 @@ using namespace cgxh;
 
 struct cgx_ctx {
     int64_t n = 0, lda = 0;
-    int op = 0;        // OP_DENSE or OP_POISSON
+    int op = 0;        // OP_DENSE, OP_POISSON or OP_CSR
+    // cgx_create_csr: room for csr_cap entries; csr_nnz = the entries of the
+    // matrix cgx_set_csr uploaded (-1: none yet, nothing may multiply);
+    // csr_plan_user: cgx_set_matvec_plan chose the plan (cgx_set_csr keeps it)
+    int64_t csr_cap = 0, csr_nnz = -1;
+    bool csr_plan_user = false;
     int64_t m = 0;     // Poisson grid width (n = m*m)
     int nranks = 1;
     int flags = 0;
@@ -495,6 +503,9 @@ int nrhs_iterate(cgx_ctx *c, int64_t count, double eps, int64_t *done, int *conv
 int nrhs_solve(cgx_ctx *c, void *x_inout, double eps, int64_t max_iter, cgx_stats *st);
 int nrhs_get_stats(cgx_ctx *c, cgx_stats *st);
 int nrhs_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu);
+// cgx_csr.hip
+int csr_need_matrix(const cgx_ctx *c, const char *what);  // CGX_ERR_STATE before the first cgx_set_csr
+int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu);
 // cgx_api.hip
 int dev_ws(RedWs *out);
 int check_dtype(int dtype, bool matvec = false);  // matvec: CGX_A_F32 is a dtype too

@@ -108,7 +108,12 @@ int matvec_sym_streamed(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, in
 int launch_matvec(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, int dot_slot, bool gated) {
     TRY(timing_begin(c, s));
     const bool streamed = (c->flags & CGX_HOST_STREAM) != 0;
-    if (c->op == OP_POISSON)
+    if (c->op == OP_CSR)  // the indices were checked on the host before they were uploaded (cgx_set_csr)
+        HIPT(spmv_csr_f64(s.plan, reinterpret_cast<const int64_t *>(s.csr_rp),
+                          reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), s.nloc, f64(vec), f64(s.Ap),
+                          with_dot ? f64(s.pown) : nullptr, with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream,
+                          gate_of(s, gated)));
+    else if (c->op == OP_POISSON)
         HIPT(stencil5_f64(f64(vec), s.nloc / c->m, c->m, f64(s.Ap), with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws,
                           s.stream, gate_of(s, gated)));
     else if (streamed && (c->flags & CGX_SYMMETRIC))
@@ -621,6 +626,7 @@ int cgx_solve_begin(cgx_ctx *c) {
     const Range range_("cgx_solve_begin");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
     if (c->nr) return nrhs_begin(c);
+    TRY(csr_need_matrix(c, "cgx_solve_begin"));
     return do_begin(c);
 }
 
@@ -751,6 +757,7 @@ int cgx_solve(cgx_ctx *c, void *x_inout, double eps, int64_t max_iter, cgx_stats
     const Range range_("cgx_solve");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
     if (c->nr) return nrhs_solve(c, x_inout, eps, max_iter, st);
+    TRY(csr_need_matrix(c, "cgx_solve"));
     if (x_inout) TRY(cgx_set_x(c, x_inout));
     TRY(sync_all(c));
     const auto t0 = std::chrono::steady_clock::now();
@@ -836,6 +843,7 @@ void *cgx_stream(cgx_ctx *c) { return c ? (void *)c->sh[0].stream : nullptr; }
 int cgx_set_matvec_plan(cgx_ctx *c, int rows_per_wave, int chunks_in_flight, int nontemporal, int blocks_per_cu) {
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
     if (c->nr) return nrhs_set_plan(c, rows_per_wave, chunks_in_flight, nontemporal, blocks_per_cu);
+    if (c->op == OP_CSR) return csr_set_plan(c, rows_per_wave, chunks_in_flight, nontemporal, blocks_per_cu);
     if (f32ref(c) || c->op != OP_DENSE || (c->flags & CGX_SYMMETRIC))
         return fail(CGX_ERR_ARG, "only the fp64 row-major dense matVec has a tunable plan");
     const int R = rows_per_wave, U = chunks_in_flight;
@@ -887,6 +895,7 @@ int cgx_residual_norm(cgx_ctx *c, double *rnorm, double *bnorm) {
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
     if (c->nr)
         return fail(CGX_ERR_ARG, "cgx_residual_norm: an nrhs context has one residual per system (cgx_residual_norms)");
+    TRY(csr_need_matrix(c, "cgx_residual_norm"));
     TRY(check_x_complete(c));
     // ||b - A x|| with the current x: allgather x, matVec, residual, two dots.
     TRY(settle_halo(c));

@@ -74,6 +74,7 @@ struct MatvecPlan {
     int small = 0;    // > 0: k_matvec_small_f64 with this many threads per block (vector in LDS)
     int a32 = 0;      // 1: k_matvec_a32's plan (float A; U counts 256-column chunks, nt is 2 or 8)
     int nrhs = 0;     // > 0: k_matvec_nrhs_f64's plan for this many vectors per pass (2, 4 or 8; nt is 2 or 8)
+    int csr = 0;      // 1: k_spmv_csr_f64's plan (R = 64 / T rows per wave, U = 1, nt is 2 or 8)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -191,6 +192,21 @@ hipError_t nrhs_update_r_f64(int64_t n, int64_t ld, int nrhs, int64_t k, double 
 // column that goes on gets p_j = r_j + beta_j p_j.
 hipError_t nrhs_update_xp_f64(int64_t n, int64_t ld, int nrhs, int64_t k, double eps, double *x, double *p,
                               const double *r, NrhsScal *sc, int64_t *hrec, hipStream_t s);
+
+// ---- sparse A in CSR storage (cgx_spmv.hip) --------------------------------------
+// out[i] = sum over e in [row_ptr[i], row_ptr[i+1]) of values[e] * v[col_idx[e]],
+// entries in stored order, T = 64 / pl.R lanes per row (the order contract is
+// in cgx_spmv.hip); pown != nullptr: also *dot_out = pown . out (fixed order
+// for a fixed grid).  The indices are not range-checked here (cgx_csr_check).
+// The instantiated (T, policy): T in {2, 4, 8, 16, 32, 64}, policy 2 or 8.
+bool spmv_csr_plan_ok(int T, int nt);
+// T <= 0 / nt < 0 / blocks_per_cu <= 0 pick the defaults (T from the mean row
+// length nnz / rows, 8 when nnz < 0; env CGX_SPMV_PLAN="T=..,nt=..,bpc=.." may override with an
+// instantiated plan).
+MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T = 0, int nt = -1, int blocks_per_cu = 0);
+hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+                        int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
+                        const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
 
 // r = b - Ax; p = r (if p); *rr_out = r.r (if rr_out).  Ax == nullptr: Ax = 0
 // (r = b - 0.0).  clear2: two int64 the kernel zeroes (the convergence record).
@@ -369,15 +385,16 @@ hipError_t preload_ref_f32();
 hipError_t preload_symv();
 hipError_t preload_matvec_a32();
 hipError_t preload_matvec_nrhs();
+hipError_t preload_spmv();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
-    PL_MATVEC_NRHS = 64
+    PL_MATVEC_NRHS = 64, PL_SPMV = 128
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
-        {PL_MATVEC_NRHS, preload_matvec_nrhs}};
+        {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

@@ -21,6 +21,7 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
     {  // the code objects this context launches from (fp64 residual checks use the vector kernels too)
         unsigned set = PL_VECTOR;
         if (c->op == OP_POISSON) set |= PL_POISSON;
+        else if (c->op == OP_CSR) set |= PL_SPMV;
         else if (f32ref(c)) set |= PL_REF_F32;
         else if (c->flags & CGX_SYMMETRIC) set |= PL_SYMV;
         else if (a32(c)) set |= PL_MATVEC_A32;
@@ -45,6 +46,12 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
     };
     if (c->op == OP_POISSON) {
         // matrix-free: no A
+    } else if (c->op == OP_CSR) {
+        // the three CSR arrays instead of A; row_ptr zeroed = every row empty until cgx_set_csr
+        TRY(dmalloc(&s.csr_rp, (size_t)(s.nloc + 1) * 8));
+        HIPT(hipMemsetAsync(s.csr_rp, 0, (size_t)(s.nloc + 1) * 8, s.stream));
+        TRY(dmalloc(&s.csr_ci, (size_t)c->csr_cap * 4));
+        TRY(dmalloc(&s.csr_val, (size_t)c->csr_cap * 8));
     } else if ((c->flags & CGX_SYMMETRIC) && (c->flags & CGX_HOST_STREAM)) {
         // the upper-triangle tiles in pinned host memory, streamed in chunks of
         // whole tiles through kStreamBufs device buffers (tile_rows = tiles per chunk)
@@ -200,7 +207,9 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
     if (c->mode == M_RCCL)
         for (auto &e : s.ev_prog)  // liveness only: the host asks whether the stream got this far
             HIPT(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
-    if (a32(c)) {
+    if (c->op == OP_CSR) {
+        s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_cap);  // cgx_set_csr plans again for the matrix it gets
+    } else if (a32(c)) {
         s.plan = plan_matvec_a32(s.dev, s.nloc, 0, 0, -1, 0, c->lda);
     } else if (!f32ref(c) && c->op == OP_DENSE && !(c->flags & CGX_SYMMETRIC)) {
         s.plan = plan_matvec_f64(s.dev, s.nloc, 0, 0, -1, 0, c->lda);
@@ -222,7 +231,7 @@ void free_shard(Shard &s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm) ncclCommDestroy(s.comm);
     for (char *p : {s.A, s.b, s.x, s.rh ? s.rh : s.r, s.p2, s.p3, s.Ap, s.pfull, s.p_alt, s.xfull, s.scal, s.sym_prow,
-                    s.sym_pcol, s.sym_stage})
+                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val})
         if (p) (void)hipFree(p);
     if (s.ws.partials) (void)hipFree(s.ws.partials);
     if (s.ws.tickets) (void)hipFree(s.ws.tickets);
@@ -668,6 +677,42 @@ int cgx_create_nrhs(cgx_ctx **ctx, int64_t n, int nrhs, int device, int flags) {
     return finish_create(c, ctx);
 }
 
+// A sparse A in CSR storage (cgx_csr.hip, cgx_spmv.hip): a cgx_create context
+// -- one GPU, one shard, the same vectors, scalars, stream and events -- that
+// owns row_ptr / col_idx / values with room for nnz entries instead of a
+// dense A.  The arguments are checked before any device is touched.
+int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags) {
+    if (!ctx) return fail(CGX_ERR_ARG, "cgx_create_csr: ctx is NULL");
+    *ctx = nullptr;
+    if (n < 1) return fail(CGX_ERR_ARG, "cgx_create_csr: n must be >= 1 (got %lld)", (long long)n);
+    if (nnz < 0) return fail(CGX_ERR_ARG, "cgx_create_csr: nnz must be >= 0 (got %lld)", (long long)nnz);
+    if (n > (int64_t)INT32_MAX)
+        return fail(CGX_ERR_ARG, "cgx_create_csr: n must be below 2^31, col_idx is int32 (got %lld)", (long long)n);
+    const struct {
+        int bit;
+        const char *name;
+    } refused[] = {{CGX_F32_REF, "CGX_F32_REF"},         {CGX_A_F32, "CGX_A_F32"},
+                   {CGX_SYMMETRIC, "CGX_SYMMETRIC"},     {CGX_HOST_STREAM, "CGX_HOST_STREAM"},
+                   {CGX_PHASES, "CGX_PHASES"},           {CGX_COMM_P2P, "CGX_COMM_P2P"},
+                   {CGX_NO_OVERLAP, "CGX_NO_OVERLAP"},   {CGX_DETERMINISTIC, "CGX_DETERMINISTIC"}};
+    for (const auto &r : refused)
+        if (flags & r.bit)
+            return fail(CGX_ERR_ARG, "cgx_create_csr: CGX_F64 (optionally with CGX_TIMING) only, not %s", r.name);
+    if (flags & ~CGX_TIMING)
+        return fail(CGX_ERR_ARG, "cgx_create_csr: CGX_F64 (optionally with CGX_TIMING) only (flags 0x%x)", flags);
+    TRY(check_device(device));
+    cgx_ctx *c = new_ctx_op(OP_CSR, n, 0, 1, flags);
+    if (!c) return fail(CGX_ERR_NOMEM, "host allocation failed");
+    c->csr_cap = nnz;
+    c->mode = M_SINGLE;
+    c->sh.resize(1);
+    c->sh[0].dev = device;
+    c->sh[0].index = 0;
+    c->sh[0].row0 = 0;
+    c->sh[0].nloc = n;
+    return finish_create(c, ctx);
+}
+
 int cgx_get_unique_id(cgx_unique_id *id) {
     if (!id) return fail(CGX_ERR_ARG, "id is NULL");
     static_assert(sizeof(ncclUniqueId) == sizeof(cgx_unique_id), "unique id size");
@@ -755,6 +800,7 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
                   ((c->mode == M_LOCAL && c->xchg_kernels) ? CGX_PULL_ACTIVE : 0) |
                   ((c->fuse_combine || c->fuse_f32) ? CGX_FOLDED_ACTIVE : 0) | (c->halo_pull ? CGX_HALO_PULL_ACTIVE : 0) |
                   (c->pool ? CGX_THREADS_ACTIVE : 0) | (c->halo_overlap ? CGX_HALO_OVERLAP_ACTIVE : 0);
+    if (c->op == OP_CSR) info->flags |= CGX_CSR_ACTIVE;
     info->elem_bytes = c->es;
     return CGX_OK;
 }
@@ -800,6 +846,8 @@ int cgx_set_rows(cgx_ctx *c, int64_t row0, int64_t nrows, const void *A_rows, in
         return fail(CGX_ERR_SHAPE, "rows [%lld, %lld) outside [0, %lld)", (long long)row0,
                     (long long)(row0 + nrows), (long long)c->n);
     if (A_rows && c->op == OP_POISSON) return fail(CGX_ERR_ARG, "the Poisson operator is matrix-free: A must be NULL");
+    if (A_rows && c->op == OP_CSR)
+        return fail(CGX_ERR_ARG, "a cgx_create_csr context takes no dense A: A must be NULL (use cgx_set_csr)");
     if (A_rows && lda_host < c->n) return fail(CGX_ERR_ARG, "lda_host (%lld) < n", (long long)lda_host);
     const size_t es = (size_t)c->es, aes = (size_t)c->aes;  // vectors / A (CGX_A_F32: 8 / 4)
     // A host-streamed A is rewritten in place on the host: first let every
@@ -889,6 +937,8 @@ int cgx_generate_spd(cgx_ctx *c, uint64_t seed) {
     const Range range_("cgx_generate_spd");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
     if (c->op == OP_POISSON) return fail(CGX_ERR_ARG, "the Poisson operator has no matrix to generate (use cgx_fill)");
+    if (c->op == OP_CSR)
+        return fail(CGX_ERR_ARG, "cgx_generate_spd: a cgx_create_csr context has no dense generator (use cgx_set_csr)");
     if (c->flags & CGX_HOST_STREAM) TRY(sync_all(c));  // copies of enqueued iterations still read A_host
     for (auto &s : c->sh) {
         TRY(set_dev(s));

@@ -94,6 +94,38 @@
  *   - One GPU, CGX_F64, A resident row-major, optionally CGX_TIMING; every
  *     other flag bit is CGX_ERR_ARG.  No creation warm-up.
  *
+ * Sparse A (cgx_create_csr): a general sparse SPD matrix in CSR storage, the
+ * matrix CG is mostly used on; the reference has none (it holds every A
+ * dense).  One GPU, fp64.
+ *   - Storage: row_ptr is int64_t[n + 1] (the entry count may pass 2^31),
+ *     col_idx int32_t[nnz] (so n < 2^31), values double[nnz]; row i owns the
+ *     entries [row_ptr[i], row_ptr[i+1]).
+ *   - Entries are taken in stored order: columns need not be sorted, and a
+ *     duplicate column is two terms of the sum.  An empty row gives +0.0.
+ *   - Summation order (k_spmv_csr_f64, T lanes per row, T = 2 .. 64): with
+ *     s = row_ptr[i], sub-lane l starts from +0.0 and adds entries s+l,
+ *     s+l+T, s+l+2T, ... in that order with one fp64 FMA each; the T partial
+ *     sums are combined as v[l] += v[l ^ o] for o = T/2, ..., 1.  A row's sum
+ *     depends on T only -- not on the load policy, the grid or the row's place
+ *     in a wave; different T agree to fp64 rounding.  The fused p.Ap adds the
+ *     blocks' partials in block order: its last bits follow the grid size.
+ *   - The structure is checked on the host (cgx_csr_check) by cgx_set_csr
+ *     before anything is uploaded; the kernel does not range-check col_idx.
+ *     The matrix is not checked for symmetry or definiteness (no mode does).
+ *   - The iteration is the three-launch one (matVec with fused p.Ap, r, x/p)
+ *     in every host form -- device-gated, CGX_GATED=0, fixed count, in pieces
+ *     -- so x is the same bits across them for a given plan.  No two-launch
+ *     small-n forms, no creation warm-up.
+ *   - Refused: cgx_set_rows / cgx_set_system with a non-NULL A and
+ *     cgx_generate_spd (CGX_ERR_ARG); cgx_solve_begin, cgx_solve and
+ *     cgx_residual_norm before the first cgx_set_csr (CGX_ERR_STATE); every
+ *     flag bit but CGX_TIMING at creation (CGX_ERR_ARG).  b and x go in
+ *     through cgx_set_rows (A_rows = NULL), cgx_set_x, cgx_fill.
+ *   - cgx_set_matvec_plan: rows_per_wave = 64 / T in {1, 2, 4, 8, 16, 32},
+ *     chunks_in_flight = 1, load policy 2 or 8; anything else is CGX_ERR_ARG
+ *     and leaves the plan as it was.  cgx_get_info: lda = the vectors' pitch,
+ *     elem_bytes = 8, flags carries CGX_CSR_ACTIVE.
+ *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
  * the p vector is allgathered and the two scalars p.Ap and r.r are
@@ -114,7 +146,9 @@ extern "C" {
 #define CGX_VERSION 101 /* 0.1.1: cgx_overlap_info gained the end-to-end form times; CGX_A_F32 added (a new
                            flag bit: no existing call changes meaning); cgx_create_nrhs and its
                            entry points added (new functions only: no struct changes size, no
-                           existing call changes meaning, so the version stays) */
+                           existing call changes meaning, so the version stays); likewise
+                           cgx_create_csr and its entry points, and the reported bit
+                           CGX_CSR_ACTIVE */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -231,6 +265,8 @@ extern "C" {
                                     the comm stream beside k_poisson_p's
                                     interior (CGX_HALO_OVERLAP=0: before it) */
 
+#define CGX_CSR_ACTIVE 0x8000000   /* reported in cgx_info.flags: a cgx_create_csr context */
+
 typedef struct cgx_ctx cgx_ctx;
 
 /* Opaque RCCL bootstrap id (ncclUniqueId is 128 bytes). */
@@ -239,7 +275,8 @@ typedef struct { char bytes[128]; } cgx_unique_id;
 typedef struct {
     int64_t n;            /* global system size                               */
     int64_t lda;          /* device leading dimension (n rounded up to 128;
-                             CGX_A_F32: to 256, in floats)                     */
+                             CGX_A_F32: to 256, in floats; cgx_create_csr:
+                             the vectors' pitch)                               */
     int     nranks;       /* row blocks in the whole job                      */
     int     nshards;      /* row blocks driven by this process                */
     int     rank0;        /* global index of this process's first row block   */
@@ -417,6 +454,17 @@ int cgx_get_stats_rhs(cgx_ctx *ctx, int j, cgx_stats *st);
  * a solve in progress.  (Any other context: one entry, cgx_residual_norm's.) */
 int cgx_residual_norms(cgx_ctx *ctx, double *rnorm, double *bnorm);
 
+/* ---- sparse A in CSR storage (see "Sparse A" above) ---------------------------- */
+/* Host-only: CGX_OK, or CGX_ERR_SHAPE with the first offence named in cgx_last_error():
+ * row_ptr[0] != 0, row_ptr decreasing at row i, row_ptr[n] != nnz, col_idx[e] outside [0, n). */
+int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col_idx);
+/* One GPU, fp64, A as CSR with room for nnz entries.  flags: CGX_F64, optionally CGX_TIMING.
+ * n < 2^31.  The arguments are checked before any device is touched. */
+int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags);
+/* Host arrays (row_ptr[n] entries, at most the context's nnz); runs cgx_csr_check first and
+ * uploads nothing when it fails (an earlier matrix stays as it was).  Ends a solve in progress. */
+int cgx_set_csr(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, const double *values);
+
 int cgx_destroy(cgx_ctx *ctx);
 int cgx_get_info(const cgx_ctx *ctx, cgx_info *info);
 int cgx_get_comm_info(cgx_ctx *ctx, cgx_comm_info *info);
@@ -518,6 +566,12 @@ int cgx_matvec(int dtype, const void *A, int64_t lda, int64_t rows, int64_t cols
  * Column j of Out is cgx_matvec(CGX_F64)'s result on column j of V bit for bit. */
 int cgx_matvec_nrhs(const void *A, int64_t lda, int64_t rows, int64_t cols, int nrhs,
                     const void *V, int64_t ldv, void *Out, int64_t ldo, void *stream);
+/* Kernel-level, device pointers, as cgx_matvec: out[i] = sum_e values[e] * v[col_idx[e]]
+ * over e in [row_ptr[i], row_ptr[i+1]), i < rows; v has cols entries.
+ * The indices must have passed cgx_csr_check: the kernel does not range-check them.
+ * T comes from CGX_SPMV_PLAN="T=..,nt=..,bpc=.." (default T = 8). */
+int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
+                 const void *values, const void *v, void *out, void *stream);
 /* vecVec: *out_dev = a . b */
 int cgx_dot(int dtype, int64_t n, const void *a, const void *b, void *out_dev, void *stream);
 /* residual x2 + vecVec: r = b - Ax; p = b - Ax; *rr_dev = r.r (rr_dev may be NULL) */
