@@ -39,6 +39,7 @@ __all__ = [
     "device_pci_bus_id", "device_link",
     "CGX_MAX_NRHS", "matVec_nrhs",
     "CGX_CSR_ACTIVE", "spmv_csr",
+    "CGX_PRECOND_ACTIVE", "PRECOND_KINDS",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
     "count_text", "read_dims", "device_count", "get_unique_id", "DeviceArray",
 ]
@@ -66,6 +67,10 @@ CGX_HALO_PULL_ACTIVE = 0x1000000
 CGX_THREADS_ACTIVE = 0x2000000
 CGX_HALO_OVERLAP_ACTIVE = 0x4000000
 CGX_CSR_ACTIVE = 0x8000000  # reported in info.flags: a cgx_create_csr context (Solver(n, csr_nnz=...))
+CGX_PRECOND_ACTIVE = 0x10000000  # reported in info.flags: a CSR context iterating with a diagonal preconditioner
+# cgx_set_precond's kinds, CGX_PC_NONE / CGX_PC_JACOBI / CGX_PC_DIAG (include/cgx.h), by the names Solver.precond
+# reports.  Kept out of the CGX_* names: those are the flag words, and a kind is not a bit of one.
+PRECOND_KINDS = {"none": 0, "jacobi": 1, "diag": 2}
 CGX_MAX_NRHS = 8  # cgx_create_nrhs: systems solved together on one matrix
 
 # cgx_phase_times indices (include/cgx.h), in the order the phases tile an iteration
@@ -176,6 +181,11 @@ def lib() -> ctypes.CDLL:
         "cgx_create_csr": ([pctx, i64, i64, i32, i32], i32),
         "cgx_set_csr": ([vp, vp, vp, vp], i32),
         "cgx_spmv_csr": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
+        "cgx_precond_diag_check": ([i64, vp], i32),
+        "cgx_set_precond": ([vp, i32], i32),
+        "cgx_set_precond_diag": ([vp, vp], i32),
+        "cgx_get_precond": ([vp, ctypes.POINTER(i32)], i32),
+        "cgx_get_precond_diag": ([vp, vp], i32),
         "cgx_get_unique_id": ([ctypes.POINTER(UniqueId)], i32),
         "cgx_rccl_available": ([], i32),
         "cgx_create_rank": ([pctx, i64, i32, i32, ctypes.POINTER(UniqueId), i32, i32], i32),
@@ -554,13 +564,17 @@ class Solver:
         self._h = h.value
 
     @classmethod
-    def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64) -> "Solver":
-        """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)."""
+    def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64,
+                 precond=None) -> "Solver":
+        """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)
+        and, with ``precond`` ("jacobi" or an array), its preconditioner (:meth:`set_precond`)."""
         rp, ci, va = _csr_arrays(indptr, indices, data)
         _need(rp.size >= 2, "from_csr: indptr needs n + 1 >= 2 entries")
         s = cls(rp.size - 1, flags=flags, device=device, csr_nnz=int(ci.size))
         try:
             s.set_csr(rp, ci, va)
+            if precond is not None:
+                s.set_precond(precond)
         except Exception:
             s.close()
             raise
@@ -575,6 +589,37 @@ class Solver:
         _need(rp.size == self.n + 1, f"set_csr: indptr has {rp.size} entries, n + 1 = {self.n + 1} needed")
         _need(ci.size <= self.csr_nnz, f"set_csr: {ci.size} entries, the solver has room for {self.csr_nnz}")
         _check(lib().cgx_set_csr(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr")
+
+    def set_precond(self, precond) -> None:
+        """Diagonal preconditioning of a ``csr_nnz`` solver: ``"jacobi"`` (1 / diag(A),
+        taken from the matrix on the device; CgxError(-4) names the lowest row whose
+        diagonal is missing, not finite or not > 0, and nothing changes), ``None``
+        (off), or an array of n positive float64 values (cgx_set_precond_diag).
+        Ends a solve in progress; :meth:`set_csr` turns it off again."""
+        L = lib()
+        if precond is None:
+            _check(L.cgx_set_precond(self._h, PRECOND_KINDS["none"]), "cgx_set_precond")
+        elif isinstance(precond, str):
+            _need(precond == "jacobi", f'set_precond: "jacobi", None or an array (got {precond!r})')
+            _check(L.cgx_set_precond(self._h, PRECOND_KINDS["jacobi"]), "cgx_set_precond")
+        else:
+            m = np.asarray(precond)
+            _need(m.dtype == np.float64, f"set_precond: the values must be float64 (got {m.dtype})")
+            _need(m.shape == (self.n,), f"set_precond: {m.shape} values, ({self.n},) needed")
+            _check(L.cgx_set_precond_diag(self._h, _ptr(np.ascontiguousarray(m))), "cgx_set_precond_diag")
+
+    @property
+    def precond(self) -> str:
+        """"none", "jacobi" or "diag" ("none" on every solver that is not a CSR one)."""
+        k = ctypes.c_int(0)
+        _check(lib().cgx_get_precond(self._h, ctypes.byref(k)), "cgx_get_precond")
+        return next(name for name, kind in PRECOND_KINDS.items() if kind == k.value)
+
+    def precond_diag(self) -> np.ndarray:
+        """The n values of M^-1 in use (CgxError(-6) when preconditioning is off)."""
+        out = np.empty(self.n, np.float64)
+        _check(lib().cgx_get_precond_diag(self._h, _ptr(out)), "cgx_get_precond_diag")
+        return out
 
     def _vshape(self, rows: int | None = None) -> tuple:
         """The shape of a b or x argument: (n,), or (nrhs, n) on an nrhs context."""

@@ -39,7 +39,8 @@
  * --csr (one GPU, fp64: the dense text matrix is read as always, only its
  * entries that are not +-0 are kept, compressed to CSR row block by row block
  * as they are parsed, and the solve runs through a cgx_create_csr context;
- * --stats adds "nnz: <count>").
+ * --stats adds "nnz: <count>"); with it --jacobi (cgx_set_precond: the
+ * solve is preconditioned with 1 / diag(A); --stats adds "precond: jacobi").
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -121,7 +122,8 @@ static void usage(const char *prog) {
             "          [--threads T] [--print-x] [--stats] matrixA vectorb initialguess\n"
             "       %s --spd N [--seed S] [--gpus P] [--a-fp32] [--eps E] [--max-iter M] [--stats]\n"
             "       %s --nrhs K ... (one GPU, fp64: K systems on one matrix; vectorb and initialguess hold K*N values)\n"
-            "       %s --csr ... (one GPU, fp64: the matrix's non-zero entries only, solved as a sparse CSR system)\n",
+            "       %s --csr [--jacobi] ... (one GPU, fp64: the matrix's non-zero entries only, solved as a sparse CSR\n"
+            "          system; --jacobi: preconditioned with 1 / diag(A))\n",
             prog, prog, prog, prog);
 }
 
@@ -325,7 +327,7 @@ static int opt_double(const char *name, const char *v, double *out) {
 
 int main(int argc, char **argv) {
     const double t_prog0 = now_s();
-    int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0, a_fp32 = 0, csr = 0;
+    int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0, a_fp32 = 0, csr = 0, jacobi = 0;
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
@@ -347,6 +349,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "--a-fp32")) a_fp32 = 1;
         else if (!strcmp(a, "--p2p")) p2p = 1;
         else if (!strcmp(a, "--csr")) csr = 1;
+        else if (!strcmp(a, "--jacobi")) jacobi = 1;
         else if (!strcmp(a, "--eps") && has_val) {
             if (!opt_double(a, argv[++i], &eps)) return 2;
         } else if (!strcmp(a, "--max-iter") && has_val) {
@@ -393,6 +396,10 @@ int main(int argc, char **argv) {
     }
     if (nrhs > 0 && (fp32ref || a_fp32 || symmetric || gpus != 1 || p2p)) {
         fprintf(stderr, "--nrhs is fp64 on one GPU with A resident (no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p)\n");
+        return 2;
+    }
+    if (jacobi && (!csr || fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
+        fprintf(stderr, "--jacobi preconditions a --csr solve (fp64 on one GPU from a matrix file: no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
         return 2;
     }
     if (csr && (fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
@@ -616,6 +623,10 @@ int main(int argc, char **argv) {
     } else if (csr) {
         rc = cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, csrm.values);
         if (rc != CGX_OK) return die_cgx(rc, "cgx_set_csr");
+        if (jacobi) { /* 1 / diag(A) from the uploaded matrix; a diagonal it refuses ends the run */
+            rc = cgx_set_precond(ctx, CGX_PC_JACOBI);
+            if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond");
+        }
         rc = cgx_set_rows(ctx, 0, n, NULL, n, b, x);
         t_dist1 = now_s();
         free(b);
@@ -669,6 +680,7 @@ int main(int argc, char **argv) {
         printf("iterations: %lld converged: %d residual_norm: %.6e\n", (long long)st.iterations, st.converged,
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
     if (stats && csr) printf("nnz: %lld\n", (long long)csrm.nnz);
+    if (stats && jacobi) printf("precond: jacobi\n");
     if (stats && nrhs > 0)
         for (int j = 0; j < (int)nrhs; ++j) {
             cgx_stats sj;

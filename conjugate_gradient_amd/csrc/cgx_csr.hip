@@ -6,6 +6,10 @@
 // The kernel reads v[col_idx[e]] unchecked, so the structure is checked on the
 // host (cgx_csr_check) before anything is uploaded: no path of a context
 // reaches the kernel with indices that did not pass.
+//
+// cgx_set_precond / cgx_set_precond_diag put n positive values minv on the
+// device (1 / diag(A) extracted there, or the caller's); while they are set,
+// do_begin and the two update launches run the PCG kernels (cgx_pcg.hip).
 #include "cgx_ctx.h"
 
 namespace cgxh {
@@ -28,9 +32,133 @@ int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
     return CGX_OK;
 }
 
+// The preconditioner's buffer goes (cgx_set_csr, cgx_set_precond(CGX_PC_NONE)); the stream is idle.
+static int pc_drop(cgx_ctx *c) {
+    Shard &s = c->sh[0];
+    c->pc_kind = CGX_PC_NONE;
+    if (s.pc_minv) {
+        TRY(set_dev(s));
+        HIPT(hipFree(s.pc_minv));
+        s.pc_minv = nullptr;
+    }
+    return CGX_OK;
+}
+
+// What every call that sets a preconditioner checks first.
+static int pc_need_csr(const cgx_ctx *c, const char *what) {
+    if (!c) return fail(CGX_ERR_ARG, "%s: ctx is NULL", what);
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "%s: not a cgx_create_csr context", what);
+    return csr_need_matrix(c, what);
+}
+
+static int pc_alloc(const Shard &s, int64_t n, char **out) {
+    const hipError_t e = hipMalloc(out, (size_t)n * 8);
+    if (e != hipSuccess)
+        return fail(CGX_ERR_NOMEM, "hipMalloc(%zu bytes) on device %d: %s", (size_t)n * 8, s.dev, hipGetErrorString(e));
+    return CGX_OK;
+}
+
+// CGX_PC_JACOBI: 1 / diag(A) from the CSR arrays into a fresh buffer, which
+// replaces the context's only when every row passed (k_csr_diag_minv).
+static int pc_jacobi(cgx_ctx *c) {
+    Shard &s = c->sh[0];
+    TRY(sync_all(c));
+    TRY(set_dev(s));
+    HIPT(preload_kernels(PL_PCG));
+    char *fresh = nullptr;
+    TRY(pc_alloc(s, c->n, &fresh));
+    auto run = [&]() -> int {
+        unsigned long long *pin = reinterpret_cast<unsigned long long *>(s.h_pin);
+        pin[0] = ~0ull;
+        HIPT(hipMemcpyAsync(slot(s, S_PCBAD), pin, 8, hipMemcpyHostToDevice, s.stream));
+        HIPT(csr_diag_minv_f64(c->n, reinterpret_cast<const int64_t *>(s.csr_rp),
+                               reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(fresh),
+                               static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
+        HIPT(hipMemcpyAsync(pin, slot(s, S_PCBAD), 8, hipMemcpyDeviceToHost, s.stream));
+        HIPT(hipStreamSynchronize(s.stream));
+        const unsigned long long bad = pin[0];
+        if (bad == ~0ull) return CGX_OK;
+        HIPT(hipMemcpyAsync(s.h_pin, fresh + bad * 8, 8, hipMemcpyDeviceToHost, s.stream));  // the row's d_i
+        HIPT(hipStreamSynchronize(s.stream));
+        const double d = s.h_pin[0];
+        if (d == 0.0 && std::signbit(d))
+            return fail(CGX_ERR_SHAPE, "cgx_set_precond: row %llu has no diagonal entry (d = 0)", bad);
+        return fail(CGX_ERR_SHAPE, "cgx_set_precond: row %llu has the diagonal d = %.17g, not finite or not > 0", bad,
+                    d);
+    };
+    const int rc = run();
+    if (rc != CGX_OK) {
+        (void)hipFree(fresh);
+        return rc;
+    }
+    if (s.pc_minv) HIPT(hipFree(s.pc_minv));
+    s.pc_minv = fresh;
+    c->pc_kind = CGX_PC_JACOBI;
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
 }  // namespace cgxh
 
 extern "C" {
+
+int cgx_precond_diag_check(int64_t n, const double *minv) {
+    if (n < 1) return fail(CGX_ERR_ARG, "cgx_precond_diag_check: n must be >= 1");
+    if (!minv) return fail(CGX_ERR_ARG, "cgx_precond_diag_check: NULL pointer");
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::isfinite(minv[i]) && minv[i] > 0.0))
+            return fail(CGX_ERR_SHAPE, "cgx_precond_diag_check: minv[%lld] = %.17g is not finite or not > 0",
+                        (long long)i, minv[i]);
+    return CGX_OK;
+}
+
+int cgx_set_precond(cgx_ctx *c, int kind) {
+    const Range range_("cgx_set_precond");
+    TRY(pc_need_csr(c, "cgx_set_precond"));
+    if (kind == CGX_PC_DIAG)
+        return fail(CGX_ERR_ARG, "cgx_set_precond: CGX_PC_DIAG takes its values through cgx_set_precond_diag");
+    if (kind != CGX_PC_NONE && kind != CGX_PC_JACOBI)
+        return fail(CGX_ERR_ARG, "cgx_set_precond: kind must be CGX_PC_NONE or CGX_PC_JACOBI (got %d)", kind);
+    if (kind == CGX_PC_JACOBI) return pc_jacobi(c);
+    TRY(sync_all(c));  // iterations still enqueued read minv
+    TRY(pc_drop(c));
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
+int cgx_set_precond_diag(cgx_ctx *c, const double *minv) {
+    const Range range_("cgx_set_precond_diag");
+    TRY(pc_need_csr(c, "cgx_set_precond_diag"));
+    if (!minv) return fail(CGX_ERR_ARG, "cgx_set_precond_diag: minv is NULL");
+    TRY(cgx_precond_diag_check(c->n, minv));  // nothing changes when it fails
+    Shard &s = c->sh[0];
+    TRY(sync_all(c));
+    TRY(set_dev(s));
+    HIPT(preload_kernels(PL_PCG));
+    if (!s.pc_minv) TRY(pc_alloc(s, c->n, &s.pc_minv));
+    HIPT(hipMemcpyAsync(s.pc_minv, minv, (size_t)c->n * 8, hipMemcpyHostToDevice, s.stream));
+    HIPT(hipStreamSynchronize(s.stream));
+    c->pc_kind = CGX_PC_DIAG;
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
+int cgx_get_precond(const cgx_ctx *c, int *kind) {
+    if (!c || !kind) return fail(CGX_ERR_ARG, "cgx_get_precond: NULL argument");
+    *kind = c->op == OP_CSR ? c->pc_kind : CGX_PC_NONE;
+    return CGX_OK;
+}
+
+int cgx_get_precond_diag(cgx_ctx *c, double *minv) {
+    if (!c || !minv) return fail(CGX_ERR_ARG, "cgx_get_precond_diag: NULL argument");
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_get_precond_diag: not a cgx_create_csr context");
+    if (c->pc_kind == CGX_PC_NONE) return fail(CGX_ERR_STATE, "cgx_get_precond_diag: no preconditioner is set");
+    Shard &s = c->sh[0];
+    TRY(set_dev(s));
+    HIPT(hipMemcpyAsync(minv, s.pc_minv, (size_t)c->n * 8, hipMemcpyDeviceToHost, s.stream));
+    HIPT(hipStreamSynchronize(s.stream));
+    return CGX_OK;
+}
 
 int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col_idx) {
     if (n < 1 || nnz < 0) return fail(CGX_ERR_ARG, "cgx_csr_check: n must be >= 1 and nnz >= 0");
@@ -73,6 +201,7 @@ int cgx_set_csr(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, cons
     }
     HIPT(hipStreamSynchronize(s.stream));
     c->csr_nnz = nnz;
+    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
     if (!c->csr_plan_user) s.plan = plan_spmv_csr(s.dev, s.nloc, nnz);
     c->state = ST_IDLE;
     return CGX_OK;

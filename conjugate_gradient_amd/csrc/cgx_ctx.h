@@ -4,7 +4,7 @@
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
 //   cgx_nrhs.hip      cgx_create_nrhs contexts: several systems per pass over A
-//   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload)
+//   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload), diagonal preconditioning
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
 //
@@ -34,6 +34,7 @@
 // Scalar slots (8 bytes each; F32_REF stores a float at the slot start):
 //   RR(j)   = r_j.r_j (global)      PAP(k) = p_k.Ap_k (global)   ring of 4
 //   LRR(j), LPAP(k): this shard's partials when an exchange follows
+//   RZ(j)   = r_j.z_j (preconditioned CG on a CSR context)      ring of 4
 //   GATHER+q: the partial of shard q (ordered combine)
 #pragma once
 
@@ -145,7 +146,7 @@ bool rccl_load();
 
 namespace cgxh {
 
-constexpr int kScalSlots = 138;  // 16 ring slots, up to 112 gathered partials, 10 aux
+constexpr int kScalSlots = 143;  // 16 ring slots, up to 112 gathered partials, 10 aux, 5 of PCG
 constexpr int kMaxShards = 32;
 // choose_overlap: the overlapped form runs when its measured time is below
 // (1 - kOverlapMargin) x the plain form's (cgx_overlap_info.margin)
@@ -155,6 +156,9 @@ constexpr int S_TR = 128, S_TB = 129, S_LTR = 130, S_LTB = 131;  // true-residua
 constexpr int S_XNZ = 134;  // rank mode: count of ranks whose x0 is not all zeros
 constexpr int S_XALPHA = 135;  // fused Poisson, x every D-th iteration: the alphas of the x updates left out (135, 136)
 constexpr int S_KDONE = 132, S_RRFINAL = 133;  // device-side convergence: k+1 at the break, r.r there
+// preconditioned CG (cgx_create_csr contexts): RZ(j) = r_j.z_j, a ring of 4 beside RR(j) -- the update kernels
+// store both sums of a pass kRzStride slots apart; PCBAD: the lowest row the diagonal extraction refused
+constexpr int S_RZ = 138, kRzStride = S_RZ - S_RR, S_PCBAD = 142;
 constexpr int kLookRing = 8;                    // pinned slots for the host's lagged convergence checks
 inline int ring(int64_t j) { return (int)(j & 3); }
 
@@ -184,6 +188,7 @@ struct Shard {
     char *pown = nullptr;  // this shard's p: pfull + row0 (dense, CSR) or the slab interior (Poisson)
     // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap]); no s.A
     char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
+    char *pc_minv = nullptr;  // ... and the preconditioner's n values (cgx_ctx::pc_kind != CGX_PC_NONE)
     // fused Poisson iteration: r with halo rows (r = rh + one row) and a
     // second p slab; p_k lives in pfull for even k, in p2 for odd k
     char *rh = nullptr, *p2 = nullptr;
@@ -280,6 +285,9 @@ struct cgx_ctx {
     // csr_plan_user: cgx_set_matvec_plan chose the plan (cgx_set_csr keeps it)
     int64_t csr_cap = 0, csr_nnz = -1;
     bool csr_plan_user = false;
+    // cgx_set_precond / cgx_set_precond_diag: CGX_PC_NONE, or the iteration runs the PCG kernels on
+    // sh[0].pc_minv (cgx_pcg.hip); cgx_set_csr goes back to CGX_PC_NONE
+    int pc_kind = CGX_PC_NONE;
     int64_t m = 0;     // Poisson grid width (n = m*m)
     int nranks = 1;
     int flags = 0;

@@ -1,6 +1,6 @@
 // cgx_device.h -- internal to libcgx: device and host helpers shared by the
 // kernel files (cgx_matvec.hip, cgx_vector.hip, cgx_poisson.hip,
-// cgx_ref_f32.hip, cgx_symv.hip).  Not part of the C ABI (include/cgx.h).
+// cgx_ref_f32.hip, cgx_symv.hip, cgx_pcg.hip).  Not part of the C ABI (include/cgx.h).
 #pragma once
 
 #include "cgx_kernels.h"
@@ -205,10 +205,11 @@ __device__ __forceinline__ void grid_sum_last_block(double v, double *partials, 
 // block's waves in order, the partials in its order), so a column's result
 // does not depend on K or on which column it is.  The storing lane writes its
 // K partials write-through and drains them all before the ticket
-// (kHandoffNote).
+// (kHandoffNote).  Sum j goes to out[j * out_stride] (the PCG kernels' r.r and
+// r.z live in two rings of scalar slots, cgx_pcg.hip).
 template <int K, int NT = kNT>
 __device__ __forceinline__ void grid_sum_last_block_n(const double (&v)[K], double *partials, unsigned *ticket,
-                                                      double *out, unsigned mask) {
+                                                      double *out, unsigned mask, int out_stride = 1) {
     __shared__ double red[K][NT / 64];
     __shared__ int is_last;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -225,7 +226,7 @@ __device__ __forceinline__ void grid_sum_last_block_n(const double (&v)[K], doub
 #pragma unroll
             for (int w = 1; w < NT / 64; ++w) t += red[j][w];
             t = 0.0 + t;
-            if ((mask >> j) & 1u) out[j] = t;
+            if ((mask >> j) & 1u) out[j * out_stride] = t;
         }
         return;
     }
@@ -270,7 +271,7 @@ __device__ __forceinline__ void grid_sum_last_block_n(const double (&v)[K], doub
             double t = red[j][0];
 #pragma unroll
             for (int w = 1; w < NT / 64; ++w) t += red[j][w];
-            if ((mask >> j) & 1u) out[j] = t;
+            if ((mask >> j) & 1u) out[j * out_stride] = t;
         }
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

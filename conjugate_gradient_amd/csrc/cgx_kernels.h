@@ -208,6 +208,30 @@ hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int3
                         int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
                         const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
 
+// ---- diagonally preconditioned CG on CSR contexts (cgx_pcg.hip) ---------------------
+// minv = the preconditioner's n positive values; z = minv o r is formed in
+// registers, never stored.  Both sums of a kernel come out of one pass: r.r to
+// out[0], r.z to out[stride] (ws.partials holds 2 * kMaxRedBlocks doubles).
+// Every pointer is 16-byte aligned (hipErrorInvalidValue otherwise).
+// r = b - Ax (Ax == nullptr: b - 0.0); p = minv o r; clear2 as residual_f64's.
+hipError_t pcg_residual_f64(int64_t n, const double *b, const double *Ax, const double *minv, double *r, double *p,
+                            double *out, int stride, const RedWs &ws, hipStream_t s, int64_t *clear2 = nullptr);
+// r -= alpha Ap with alpha = *rz_old / *pAp
+hipError_t pcg_update_r_f64(int64_t n, double *r, const double *Ap, const double *minv, const double *rz_old,
+                            const double *pAp, double *out, int stride, const RedWs &ws, hipStream_t s,
+                            const int64_t *gate = nullptr);
+// x += alpha p; then (rr != nullptr) p = minv o r + (*rz_new / *rz_old) p.  The
+// stopping decision is update_xp_f64's, on *rr.
+hipError_t pcg_update_xp_f64(int64_t n, double *x, double *p, const double *r, const double *minv,
+                             const double *rz_old, const double *pAp, const double *rr, const double *rz_new,
+                             hipStream_t s, double eps = -1.0, int64_t k = 0, int64_t *kdone = nullptr,
+                             double *rrfinal = nullptr, int64_t *hrec = nullptr);
+// minv[i] = 1.0 / d_i, d_i = the sum in stored order of row i's entries in
+// column i.  A row without one, or with d_i not finite or not > 0, stores d_i
+// instead (-0.0: no entry) and lowers *bad (preset to all ones) to its index.
+hipError_t csr_diag_minv_f64(int64_t n, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+                             double *minv, unsigned long long *bad, hipStream_t s);
+
 // r = b - Ax; p = r (if p); *rr_out = r.r (if rr_out).  Ax == nullptr: Ax = 0
 // (r = b - 0.0).  clear2: two int64 the kernel zeroes (the convergence record).
 hipError_t residual_f64(int64_t n, const double *b, const double *Ax, double *r, double *p,
@@ -386,15 +410,16 @@ hipError_t preload_symv();
 hipError_t preload_matvec_a32();
 hipError_t preload_matvec_nrhs();
 hipError_t preload_spmv();
+hipError_t preload_pcg();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
-    PL_MATVEC_NRHS = 64, PL_SPMV = 128
+    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
-        {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}};
+        {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

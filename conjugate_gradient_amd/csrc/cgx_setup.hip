@@ -150,7 +150,8 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
     TRY(dmalloc(&s.scal, kScalSlots * 8));
     if (c->mode == M_RCCL && c->nranks > 1) TRY(dmalloc(&s.xfull, xlen * es));
     char *part = nullptr, *tick = nullptr;
-    TRY(dmalloc(&part, kMaxRedBlocks * sizeof(double)));
+    // a CSR context's PCG kernels sum two values per pass (grid_sum_last_block_n<2>)
+    TRY(dmalloc(&part, (c->op == OP_CSR ? 2 : 1) * kMaxRedBlocks * sizeof(double)));
     s.ws.partials = reinterpret_cast<double *>(part);  // owned by the shard from here (free_shard)
     TRY(dmalloc(&tick, kTickets * sizeof(unsigned)));
     s.ws.tickets = reinterpret_cast<unsigned *>(tick);
@@ -231,7 +232,7 @@ void free_shard(Shard &s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm) ncclCommDestroy(s.comm);
     for (char *p : {s.A, s.b, s.x, s.rh ? s.rh : s.r, s.p2, s.p3, s.Ap, s.pfull, s.p_alt, s.xfull, s.scal, s.sym_prow,
-                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val})
+                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.pc_minv})
         if (p) (void)hipFree(p);
     if (s.ws.partials) (void)hipFree(s.ws.partials);
     if (s.ws.tickets) (void)hipFree(s.ws.tickets);
@@ -800,7 +801,7 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
                   ((c->mode == M_LOCAL && c->xchg_kernels) ? CGX_PULL_ACTIVE : 0) |
                   ((c->fuse_combine || c->fuse_f32) ? CGX_FOLDED_ACTIVE : 0) | (c->halo_pull ? CGX_HALO_PULL_ACTIVE : 0) |
                   (c->pool ? CGX_THREADS_ACTIVE : 0) | (c->halo_overlap ? CGX_HALO_OVERLAP_ACTIVE : 0);
-    if (c->op == OP_CSR) info->flags |= CGX_CSR_ACTIVE;
+    if (c->op == OP_CSR) info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0);
     info->elem_bytes = c->es;
     return CGX_OK;
 }

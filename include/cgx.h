@@ -125,6 +125,35 @@
  *     chunks_in_flight = 1, load policy 2 or 8; anything else is CGX_ERR_ARG
  *     and leaves the plan as it was.  cgx_get_info: lda = the vectors' pitch,
  *     elem_bytes = 8, flags carries CGX_CSR_ACTIVE.
+ *   - Diagonal preconditioning (cgx_set_precond, cgx_set_precond_diag): the
+ *     iteration becomes preconditioned CG with M^-1 = diag(minv), minv the n
+ *     positive values 1 / diag(A) (CGX_PC_JACOBI) or the caller's
+ *     (CGX_PC_DIAG).  Still three launches per iteration in every host form,
+ *     and x the same bits across the forms for a given plan: the SpMV with
+ *     p.Ap unchanged; r -= alpha Ap with r.r and r.z from one pass (alpha =
+ *     r.z_old / p.Ap, z_i = fl(minv_i r_i), a rounded product, never stored);
+ *     x += alpha p and p = z + beta p (beta = r.z_new / r.z_old, z
+ *     recomputed).  The solve starts from r = b - A x, p = minv o r.
+ *     - Refusals: a context that is not a cgx_create_csr context, an unknown
+ *       kind, CGX_PC_DIAG passed to cgx_set_precond, a NULL ctx or pointer:
+ *       CGX_ERR_ARG; a call before the first cgx_set_csr: CGX_ERR_STATE.
+ *     - A successful call ends a solve in progress, as cgx_set_csr does.
+ *     - cgx_set_csr turns preconditioning off (the diagonal belonged to the
+ *       old matrix): the caller asks for it again.
+ *     - CGX_PC_JACOBI: d_i is the sum, from +0.0 in stored order, of row i's
+ *       entries whose column is i (a duplicate is two terms, as in the SpMV);
+ *       minv_i = 1.0 / d_i, the correctly rounded fp64 quotient (the bits of
+ *       the host's 1.0 / d).  A row with no diagonal entry, or with a d_i
+ *       that is not finite or not > 0, fails the call: CGX_ERR_SHAPE naming
+ *       the lowest such row and its d_i.  The context then keeps the
+ *       preconditioner it had; a later solve gives the bits it gave before.
+ *     - The stopping rule and the stats do not change: the loop ends when
+ *       sqrt(r.r) < eps (r, not z), cgx_stats.rr is r.r, cgx_residual_norm is
+ *       the true residual.
+ *     - minv == 1.0 everywhere gives the unpreconditioned x, loop count and
+ *       r.r bit for bit on the same plan; so does minv == a power of two
+ *       (alpha absorbs the factor, p carries it).
+ *     - cgx_get_info: flags carries CGX_PRECOND_ACTIVE while a kind is set.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -148,7 +177,8 @@ extern "C" {
                            entry points added (new functions only: no struct changes size, no
                            existing call changes meaning, so the version stays); likewise
                            cgx_create_csr and its entry points, and the reported bit
-                           CGX_CSR_ACTIVE */
+                           CGX_CSR_ACTIVE; likewise cgx_set_precond and its entry points,
+                           and the reported bit CGX_PRECOND_ACTIVE */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -266,6 +296,8 @@ extern "C" {
                                     interior (CGX_HALO_OVERLAP=0: before it) */
 
 #define CGX_CSR_ACTIVE 0x8000000   /* reported in cgx_info.flags: a cgx_create_csr context */
+#define CGX_PRECOND_ACTIVE 0x10000000 /* reported in cgx_info.flags: a cgx_create_csr context iterating
+                                         with a diagonal preconditioner (cgx_set_precond) */
 
 typedef struct cgx_ctx cgx_ctx;
 
@@ -464,6 +496,18 @@ int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags)
 /* Host arrays (row_ptr[n] entries, at most the context's nnz); runs cgx_csr_check first and
  * uploads nothing when it fails (an earlier matrix stays as it was).  Ends a solve in progress. */
 int cgx_set_csr(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, const double *values);
+
+/* ---- diagonal preconditioning of a cgx_create_csr context (see "Sparse A" above) ------------- */
+#define CGX_PC_NONE   0
+#define CGX_PC_JACOBI 1   /* M^-1 = 1 / diag(A), taken from the CSR arrays on the device */
+#define CGX_PC_DIAG   2   /* M^-1 = a caller's positive vector (reported; set by cgx_set_precond_diag) */
+/* Host-only: CGX_OK, or CGX_ERR_SHAPE naming the first entry that is not finite or not > 0
+ * (CGX_ERR_ARG: n < 1 or minv NULL). */
+int cgx_precond_diag_check(int64_t n, const double *minv);
+int cgx_set_precond(cgx_ctx *ctx, int kind);            /* CGX_PC_NONE or CGX_PC_JACOBI */
+int cgx_set_precond_diag(cgx_ctx *ctx, const double *minv);   /* n host values; runs the check first */
+int cgx_get_precond(const cgx_ctx *ctx, int *kind);     /* CGX_PC_NONE on every other context */
+int cgx_get_precond_diag(cgx_ctx *ctx, double *minv);   /* the n values in use; CGX_ERR_STATE when none */
 
 int cgx_destroy(cgx_ctx *ctx);
 int cgx_get_info(const cgx_ctx *ctx, cgx_info *info);
