@@ -262,16 +262,20 @@ __device__ __forceinline__ void poisson_p_step(const double *__restrict__ rh, co
     }
 }
 
-// XCD bands (CGX_POISSON_BANDS=1, one item range of whole runs): the
+// XCD bands (`bands` of CGX_POISSON_PLAN, on by default; one item range of
+// whole runs and a grid of 8 or more blocks): the
 // blocks of XCD x (blockIdx % 8, the dispatcher's round-robin) take the
 // items of the x-th eighth of the runs, strip-fastest, so an item's left and
 // right neighbours (whose edge columns it loads as side points) and the item
 // below (whose first two rows are its last two) are fetched through the same
 // L2 at about the same time.  Without bands those neighbours are taken by
 // blocks of other XCDs.  The v-th item of this block within its band, or -1.
-// bands = 1 + rot: band x walks its items starting rot * x items in (mod its
-// count), so the eight XCDs' streams (bands 64 MiB apart at m = 8192) sit at
-// different offsets (CGX_POISSON_BAND_ROT; an experiment, as for k_symv_f64).
+// The kernels' `bands` argument is 1 + rot: band x walks its items starting
+// rot * x items in (mod its count), so the eight XCDs' streams (bands 64 MiB
+// apart at m = 8192) sit at different offsets (an experiment, as for
+// k_symv_f64).  The launchers pass 0 or 1 whatever the plan's `bands` is
+// (launch_p, launch_poisson_xr), so every nonzero value of the key runs
+// rot = 0: `bands=3` walks the items as `bands=1` does.
 struct Band {
     int64_t first, count, stride, start, rot;
 };

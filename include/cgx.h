@@ -466,7 +466,16 @@ int cgx_create_rank(cgx_ctx **ctx, int64_t n, int rank, int nranks,
  * natural row-major order.  Multi-GPU splits the grid into slabs of m/P grid
  * rows (m % P == 0) and exchanges one halo row with each neighbour per
  * iteration (ncclSend/Recv in rank mode) instead of allgathering p.
- * CGX_F64 only; set b / x0 with cgx_fill or cgx_set_rows (A must be NULL). */
+ * CGX_F64 only; set b / x0 with cgx_fill or cgx_set_rows (A must be NULL).
+ * Pinned by tests/test_gpu_poisson_probe.py on rough (random, nonzero) b and
+ * x0, one block to eight, fused and split, every x deferral, every halo
+ * exchange form and two ranks: after a fixed count of iterations every element
+ * of x agrees with sequential CG in extended precision to fp64 rounding (100 x
+ * the spread between fp64 summation orders, at most 1.2e-11 of max|x|) under
+ * every key of CGX_POISSON_PLAN; x and r.r are bit-identical across `rb` on a
+ * given grid, and the same bits when a plan runs twice; `rows`, `bands`,
+ * `reverse` and `blocks` change x only through the order in which the partial
+ * sums of p.Ap and r.r are added (`pipe` not at all). */
 int cgx_create_poisson(cgx_ctx **ctx, int64_t m, int device, int flags);
 int cgx_create_poisson_multi(cgx_ctx **ctx, int64_t m, int nshards, const int *devices, int flags);
 int cgx_create_poisson_rank(cgx_ctx **ctx, int64_t m, int rank, int nranks,

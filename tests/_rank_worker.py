@@ -52,10 +52,20 @@ def main():
         m = n
         with cg.Solver(None, poisson_m=m, rank=rank, nranks=P, unique_id=uid, device=dev) as s:
             res["comm"] = s.comm_info()
-            s.fill(1.0, 0.0)
-            eps = 1e-8 if mode == "poisson_eps" else -1.0
-            x, st = s.solve(None, eps=eps, max_iter=-1 if eps > 0 else 120)
-            res.update(iterations=st.iterations, converged=st.converged)
+            if mode == "poisson_probe":  # rough b and x0: x's halo rows differ between the ranks; 9 fixed loops
+                import _poisson_probe as pp
+                b, x0 = pp.rough(m, m)
+                s.set_rows(0, None, b, x0)
+                s.begin()
+                done, conv = s.iterate(9, -1.0)
+                x = s.get_x()
+                res.update(iterations=done, converged=conv,
+                           halo_overlap=bool(s.info.flags & cg.CGX_HALO_OVERLAP_ACTIVE))
+            else:
+                s.fill(1.0, 0.0)
+                eps = 1e-8 if mode == "poisson_eps" else -1.0
+                x, st = s.solve(None, eps=eps, max_iter=-1 if eps > 0 else 120)
+                res.update(iterations=st.iterations, converged=st.converged)
     else:
         flags = {"f32ref": cg.CGX_F32_REF, "p2p": cg.CGX_COMM_P2P, "nooverlap": cg.CGX_NO_OVERLAP,
                  "deterministic": cg.CGX_DETERMINISTIC, "headline_det": cg.CGX_DETERMINISTIC,

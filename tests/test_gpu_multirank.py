@@ -23,6 +23,7 @@ import sys
 import numpy as np
 import pytest
 
+import _poisson_probe as pp
 import conjugate_gradient_amd as cg
 import oracle
 from _cases import case, golden_mpi, hash_oracle, mpi_golden_x
@@ -153,6 +154,27 @@ def test_rank_mode_poisson_halo(tmp_path, mode):
                                    max_iter=-1 if eps > 0 else 120)
     assert res[0]["iterations"] == so.iterations
     assert rel(x, xo) <= (TOL if eps > 0 else 1e-9)
+
+
+@pytest.mark.timeout(200)
+@pytest.mark.parametrize("halo", ["default", "force"])
+def test_rank_mode_poisson_probe(tmp_path, monkeypatch, halo):
+    """Two ranks on rough data (tests/_poisson_probe.py): x0 is nonzero, so the initial stencil runs and x's
+    halo rows travel by ncclSend/Recv with different values on the two ranks (b = 1, x0 = 0 sends nothing but
+    zeros there, and the grid's mirror symmetry makes a rank's own boundary row equal to the row it should have
+    received).  x after 9 fixed loops, element by element against long-double CG to bar(130, 9); with the
+    default halo exchange and with CGX_HALO_OVERLAP=force."""
+    m, P = 130, 2
+    if halo == "force":
+        monkeypatch.setenv("CGX_HALO_OVERLAP", "force")
+    else:
+        monkeypatch.delenv("CGX_HALO_OVERLAP", raising=False)
+    x, res = run_ranks(tmp_path, "poisson_probe", m, P)
+    x_ld = pp.reference(m, "rough", 9)[0]
+    d = pp.dist(x, x_ld)
+    print(f"\n[probe] rank mode world 2 m={m} halo={halo} (overlap {res[0]['halo_overlap']}): "
+          f"x {d / pp.bar(m, 9):.3g} of the bar")
+    assert d <= pp.bar(m, 9)
 
 
 @pytest.mark.timeout(240)
