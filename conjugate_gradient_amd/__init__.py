@@ -38,7 +38,7 @@ __all__ = [
     "Solver", "lib", "build",
     "device_pci_bus_id", "device_link",
     "CGX_MAX_NRHS", "matVec_nrhs",
-    "CGX_CSR_ACTIVE", "spmv_csr",
+    "CGX_CSR_ACTIVE", "spmv_csr", "spmm_csr",
     "CGX_PRECOND_ACTIVE", "PRECOND_KINDS",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
     "count_text", "read_dims", "device_count", "get_unique_id", "DeviceArray",
@@ -181,6 +181,8 @@ def lib() -> ctypes.CDLL:
         "cgx_create_csr": ([pctx, i64, i64, i32, i32], i32),
         "cgx_set_csr": ([vp, vp, vp, vp], i32),
         "cgx_spmv_csr": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
+        "cgx_create_csr_nrhs": ([pctx, i64, i64, i32, i32, i32], i32),
+        "cgx_spmm_csr": ([i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp], i32),
         "cgx_precond_diag_check": ([i64, vp], i32),
         "cgx_set_precond": ([vp, i32], i32),
         "cgx_set_precond_diag": ([vp, vp], i32),
@@ -422,6 +424,18 @@ def _csr_arrays(indptr, indices=None, data=None):
     return rp, ci, va
 
 
+def _csr_checked(what: str, rp, ci, rows: int, cols: int) -> None:
+    """The structure check of the kernel-level CSR calls: raises unless every index is inside [0, cols)."""
+    # cgx_csr_check takes a square structure: fewer rows than columns are
+    # padded with empty rows (the same last row pointer), so the columns are
+    # checked against cols; with more rows than columns they are checked here
+    nsq = max(rows, cols)
+    rp_sq = rp if nsq == rows else np.concatenate([rp, np.full(nsq - rows, rp[-1], np.int64)])
+    _check(lib().cgx_csr_check(nsq, ci.size, _ptr(rp_sq), _ptr(ci)), "cgx_csr_check")
+    bad = np.flatnonzero(ci >= cols)
+    _need(bad.size == 0, f"{what}: indices[{bad[0] if bad.size else 0}] outside [0, {cols})")
+
+
 def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int, cols: int) -> None:
     """out[i] = sum_e data[e] * v[indices[e]] over row i's entries, in stored
     order (k_spmv_csr_f64; the plan from CGX_SPMV_PLAN).  The structure comes
@@ -434,17 +448,38 @@ def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int,
     _fits([v], cols, "spmv_csr v")
     _fits([out], rows, "spmv_csr out")
     L = lib()
-    # cgx_csr_check takes a square structure: fewer rows than columns are
-    # padded with empty rows (the same last row pointer), so the columns are
-    # checked against cols; with more rows than columns they are checked here
-    nsq = max(rows, cols)
-    rp_sq = rp if nsq == rows else np.concatenate([rp, np.full(nsq - rows, rp[-1], np.int64)])
-    _check(L.cgx_csr_check(nsq, ci.size, _ptr(rp_sq), _ptr(ci)), "cgx_csr_check")
-    bad = np.flatnonzero(ci >= cols)
-    _need(bad.size == 0, f"spmv_csr: indices[{bad[0] if bad.size else 0}] outside [0, {cols})")
+    _csr_checked("spmv_csr", rp, ci, rows, cols)
     d_rp, d_ci, d_va = DeviceArray.from_host(rp), DeviceArray.from_host(ci), DeviceArray.from_host(va)
     try:
         _check(L.cgx_spmv_csr(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, v.ptr, out.ptr, None), "cgx_spmv_csr")
+        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
+    finally:
+        for d in (d_rp, d_ci, d_va):
+            d.free()
+
+
+def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int, cols: int, nrhs: int,
+             ldv: int | None = None, ldo: int | None = None) -> None:
+    """``nrhs`` sparse matVecs in one pass over the CSR arrays (k_spmm_csr_f64; the plan from
+    CGX_SPMM_PLAN): Out[j*ldo + i] = sum_e data[e] * V[j*ldv + indices[e]].  Column j is
+    :func:`spmv_csr`'s result on column j of V bit for bit at the same T.  The structure is
+    checked on the host before anything is uploaded, as :func:`spmv_csr` does."""
+    rp, ci, va = _csr_arrays(indptr, indices, data)
+    ldv, ldo = ldv or cols, ldo or rows
+    _need(isinstance(nrhs, (int, np.integer)) and 1 <= nrhs <= CGX_MAX_NRHS,
+          f"spmm_csr: nrhs must be in [1, {CGX_MAX_NRHS}] (got {nrhs})")
+    _need(rows >= 1 and cols >= 1 and ldv >= cols and ldo >= rows,
+          "spmm_csr: need rows, cols >= 1, ldv >= cols and ldo >= rows")
+    _need(rp.size == rows + 1, f"spmm_csr: indptr has {rp.size} entries, rows + 1 = {rows + 1} needed")
+    _need(V.dtype == np.float64 and Out.dtype == np.float64, "spmm_csr: float64 only")
+    _fits([V], (nrhs - 1) * ldv + cols, "spmm_csr V")
+    _fits([Out], (nrhs - 1) * ldo + rows, "spmm_csr Out")
+    L = lib()
+    _csr_checked("spmm_csr", rp, ci, rows, cols)
+    d_rp, d_ci, d_va = DeviceArray.from_host(rp), DeviceArray.from_host(ci), DeviceArray.from_host(va)
+    try:
+        _check(L.cgx_spmm_csr(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, int(nrhs), V.ptr, ldv, Out.ptr, ldo, None),
+               "cgx_spmm_csr")
         _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
     finally:
         for d in (d_rp, d_ci, d_va):
@@ -506,7 +541,9 @@ class Solver:
     ``csr_nnz=nnz`` (cgx_create_csr): a sparse A in CSR storage with room for
     ``nnz`` entries, one GPU, fp64; the matrix goes in through :meth:`set_csr`
     (or build the solver with :meth:`from_csr`), b and x through ``set_rows``
-    / ``set_x`` / ``fill``."""
+    / ``set_x`` / ``fill``.  Several right-hand sides on a CSR matrix
+    (cgx_create_csr_nrhs) are spelled ``Solver.csr(n, nnz, nrhs=K)`` or
+    ``Solver.from_csr(..., nrhs=K)``; ``Solver(n, csr_nnz=..., nrhs=...)`` raises."""
 
     def __init__(self, n: int, *, flags: int = CGX_F64, device: int = 0, devices=None,
                  rank: int | None = None, nranks: int | None = None, unique_id: bytes | None = None,
@@ -564,13 +601,36 @@ class Solver:
         self._h = h.value
 
     @classmethod
+    def csr(cls, n: int, nnz: int, *, nrhs: int | None = None, device: int = 0, flags: int = CGX_F64) -> "Solver":
+        """An empty CSR solver with room for ``nnz`` entries (the matrix goes in through
+        :meth:`set_csr`).  ``nrhs=K`` (cgx_create_csr_nrhs): K systems on the one matrix solved
+        together, one read of the CSR arrays per iteration; b and x are then ``(K, n)`` arrays as
+        on a dense ``nrhs`` solver.  Without ``nrhs`` it is ``Solver(n, csr_nnz=nnz)``."""
+        if nrhs is None:
+            return cls(n, flags=flags, device=device, csr_nnz=nnz)
+        _need(isinstance(nrhs, (int, np.integer)) and 1 <= nrhs <= CGX_MAX_NRHS,
+              f"Solver.csr: nrhs must be in [1, {CGX_MAX_NRHS}] (got {nrhs})")
+        _need(isinstance(nnz, (int, np.integer)) and nnz >= 0, f"Solver.csr: nnz must be an integer >= 0 (got {nnz})")
+        _need(isinstance(n, (int, np.integer)) and n >= 1, f"Solver.csr: n must be an integer >= 1 (got {n})")
+        h = ctypes.c_void_p()
+        rc = lib().cgx_create_csr_nrhs(ctypes.byref(h), int(n), int(nnz), int(nrhs), device, flags)
+        _check(rc, "cgx_create_csr_nrhs")
+        s = cls.__new__(cls)  # the fields __init__ sets
+        s.nrhs, s.csr_nnz, s.poisson_m = int(nrhs), int(nnz), None
+        s.n, s.flags, s.dtype = int(n), flags, _dtype(flags)
+        s._h = h.value
+        return s
+
+    @classmethod
     def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64,
-                 precond=None) -> "Solver":
+                 precond=None, nrhs: int | None = None) -> "Solver":
         """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)
-        and, with ``precond`` ("jacobi" or an array), its preconditioner (:meth:`set_precond`)."""
+        and, with ``precond`` ("jacobi" or an array), its preconditioner (:meth:`set_precond`).
+        ``nrhs=K``: K systems on the matrix solved together (:meth:`csr`; no preconditioner)."""
         rp, ci, va = _csr_arrays(indptr, indices, data)
         _need(rp.size >= 2, "from_csr: indptr needs n + 1 >= 2 entries")
-        s = cls(rp.size - 1, flags=flags, device=device, csr_nnz=int(ci.size))
+        _need(nrhs is None or precond is None, "from_csr: no preconditioner with several right-hand sides")
+        s = cls.csr(rp.size - 1, int(ci.size), nrhs=nrhs, device=device, flags=flags)
         try:
             s.set_csr(rp, ci, va)
             if precond is not None:

@@ -48,6 +48,8 @@ static int pc_drop(cgx_ctx *c) {
 static int pc_need_csr(const cgx_ctx *c, const char *what) {
     if (!c) return fail(CGX_ERR_ARG, "%s: ctx is NULL", what);
     if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "%s: not a cgx_create_csr context", what);
+    // OP_CSR alone does not do: the K-column update kernels have no PCG form
+    if (c->nr) return fail(CGX_ERR_ARG, "%s: not with several right-hand sides (a cgx_create_csr_nrhs context)", what);
     return csr_need_matrix(c, what);
 }
 
@@ -202,7 +204,10 @@ int cgx_set_csr(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, cons
     HIPT(hipStreamSynchronize(s.stream));
     c->csr_nnz = nnz;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
-    if (!c->csr_plan_user) s.plan = plan_spmv_csr(s.dev, s.nloc, nnz);
+    if (!c->csr_plan_user) {
+        if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs));
+        else s.plan = plan_spmv_csr(s.dev, s.nloc, nnz);
+    }
     c->state = ST_IDLE;
     return CGX_OK;
 }
@@ -220,6 +225,24 @@ int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *co
     HIPT(spmv_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
                       static_cast<const double *>(values), rows, static_cast<const double *>(v),
                       static_cast<double *>(out), nullptr, nullptr, ws, static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
+int cgx_spmm_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const void *values, int nrhs,
+                 const void *V, int64_t ldv, void *Out, int64_t ldo, void *stream) {
+    if (nrhs < 1 || nrhs > CGX_MAX_NRHS)
+        return fail(CGX_ERR_ARG, "cgx_spmm_csr: nrhs must be in [1, %d] (got %d)", CGX_MAX_NRHS, nrhs);
+    if (!row_ptr || !col_idx || !values || !V || !Out) return fail(CGX_ERR_ARG, "cgx_spmm_csr: NULL pointer");
+    if (rows < 0 || cols < 0 || (nrhs > 1 && (ldv < cols || ldo < rows)))
+        return fail(CGX_ERR_SHAPE, "cgx_spmm_csr: bad shape");
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    const RedWs none{nullptr, nullptr};  // no fused dot: no reduction scratch
+    // the entry count lives on the device: T comes from CGX_SPMM_PLAN or, without it, is 8
+    const MatvecPlan pl = plan_spmm_csr(dev, rows, /*nnz=*/-1, nrhs_width(nrhs));
+    HIPT(spmm_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
+                      static_cast<const double *>(values), rows, nrhs, static_cast<const double *>(V), ldv,
+                      static_cast<double *>(Out), ldo, nullptr, 0, nullptr, none, static_cast<hipStream_t>(stream)));
     return CGX_OK;
 }
 

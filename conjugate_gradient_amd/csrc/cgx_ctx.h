@@ -3,7 +3,7 @@
 //   cgx_setup.hip     contexts and shards: create, destroy, data in and out
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
-//   cgx_nrhs.hip      cgx_create_nrhs contexts: several systems per pass over A
+//   cgx_nrhs.hip      cgx_create_nrhs / cgx_create_csr_nrhs contexts: several systems per pass over A
 //   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload), diagonal preconditioning
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
@@ -259,6 +259,9 @@ struct LocalPool;  // cgx_local_mt.hip
 // the host-mapped record as a cgx_create context's; the vectors and scalars of
 // the nrhs systems live here.  Column j of b, x, r, p, Ap starts at j * lda
 // doubles (zero past n), so p is what k_matvec_nrhs_f64 multiplies.
+// cgx_create_csr_nrhs: the same state beside a cgx_create_csr context's shard
+// (op == OP_CSR: the CSR arrays instead of A); nrhs_matvec then multiplies with
+// k_spmm_csr_f64 (cgx_spmm.hip) and `plan` is plan_spmm_csr's.
 struct NrhsState {
     int nrhs = 0;  // 1..CGX_MAX_NRHS
     char *b = nullptr, *x = nullptr, *r = nullptr, *p = nullptr, *Ap = nullptr;
@@ -499,7 +502,7 @@ bool warm_eligible(const cgx_ctx *c);
 int warm_solve_kernels(cgx_ctx *c);
 // cgx_nrhs.hip: the nrhs context's own paths; the entry points of the other
 // files branch to them at their top (c->nr != nullptr)
-int nrhs_check_args(int nrhs, int flags);
+int nrhs_check_args(int nrhs, int flags, const char *fn = "cgx_create_nrhs");  // fn: the name in the message
 int nrhs_alloc(cgx_ctx *c, int nrhs);
 void nrhs_free(cgx_ctx *c);
 int nrhs_set_vec_rows(cgx_ctx *c, int64_t row0, int64_t nrows, const void *b_rows, const void *x_rows);

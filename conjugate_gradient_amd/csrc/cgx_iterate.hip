@@ -639,8 +639,8 @@ extern "C" {
 int cgx_solve_begin(cgx_ctx *c) {
     const Range range_("cgx_solve_begin");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
-    if (c->nr) return nrhs_begin(c);
     TRY(csr_need_matrix(c, "cgx_solve_begin"));
+    if (c->nr) return nrhs_begin(c);
     return do_begin(c);
 }
 
@@ -770,8 +770,8 @@ static int iterate_calls(cgx_ctx *c, int64_t count, double eps, int64_t *done, i
 int cgx_solve(cgx_ctx *c, void *x_inout, double eps, int64_t max_iter, cgx_stats *st) {
     const Range range_("cgx_solve");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
-    if (c->nr) return nrhs_solve(c, x_inout, eps, max_iter, st);
     TRY(csr_need_matrix(c, "cgx_solve"));
+    if (c->nr) return nrhs_solve(c, x_inout, eps, max_iter, st);
     if (x_inout) TRY(cgx_set_x(c, x_inout));
     TRY(sync_all(c));
     const auto t0 = std::chrono::steady_clock::now();

@@ -208,6 +208,25 @@ hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int3
                         int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
                         const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
 
+// ---- several right-hand sides on a CSR matrix (cgx_spmm.hip) ----------------------
+// Out[j*ldo + i] = sum over row i's entries of values[e] * V[j*ldv + col_idx[e]]
+// for j < nrhs: values and col_idx loaded once per entry and multiplied by
+// K = nrhs_width(nrhs) gathered elements.  Each column sums in k_spmv_csr_f64's
+// order at the same T = 64 / pl.R, so it is spmv_csr_f64's result on that
+// column bit for bit.  pown != nullptr: also dot_out[j] = pown[j*ldp ..] .
+// Out[j*ldo ..] for every j < nrhs (ws as the nrhs kernels': kMaxNrhs *
+// kMaxRedBlocks partials).  The indices are not range-checked here.
+// The instantiated (K, T, policy): K in {2, 4, 8}, T in {2, .., 64}, policy 2 or 8.
+bool spmm_csr_plan_ok(int K, int T, int nt);
+// T <= 0 / nt < 0 / blocks_per_cu <= 0 pick the defaults (T from the mean row
+// length nnz / rows, 8 when nnz < 0; env CGX_SPMM_PLAN="T=..,nt=..,bpc=.."
+// may override with an instantiated plan).  pl.nrhs = K, pl.csr = 1.
+MatvecPlan plan_spmm_csr(int device, int64_t rows, int64_t nnz, int K, int T = 0, int nt = -1, int blocks_per_cu = 0);
+hipError_t spmm_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+                        int64_t rows, int nrhs, const double *V, int64_t ldv, double *Out, int64_t ldo,
+                        const double *pown, int64_t ldp, double *dot_out, const RedWs &ws, hipStream_t s,
+                        const int64_t *gate = nullptr, int64_t *ts = nullptr);
+
 // ---- diagonally preconditioned CG on CSR contexts (cgx_pcg.hip) ---------------------
 // minv = the preconditioner's n positive values; z = minv o r is formed in
 // registers, never stored.  Both sums of a kernel come out of one pass: r.r to
@@ -410,16 +429,18 @@ hipError_t preload_symv();
 hipError_t preload_matvec_a32();
 hipError_t preload_matvec_nrhs();
 hipError_t preload_spmv();
+hipError_t preload_spmm();
 hipError_t preload_pcg();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
-    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256
+    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
-        {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg}};
+        {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg},
+        {PL_SPMM, preload_spmm}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

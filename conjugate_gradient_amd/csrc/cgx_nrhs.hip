@@ -25,9 +25,9 @@ namespace cgxh {
 
 static double *col(char *base, const cgx_ctx *c, int j) { return f64(base) + (size_t)j * c->lda; }
 
-int nrhs_check_args(int nrhs, int flags) {
+int nrhs_check_args(int nrhs, int flags, const char *fn) {
     if (nrhs < 1 || nrhs > CGX_MAX_NRHS)
-        return fail(CGX_ERR_ARG, "cgx_create_nrhs: nrhs must be in [1, %d] (got %d)", CGX_MAX_NRHS, nrhs);
+        return fail(CGX_ERR_ARG, "%s: nrhs must be in [1, %d] (got %d)", fn, CGX_MAX_NRHS, nrhs);
     const struct {
         int bit;
         const char *name;
@@ -37,9 +37,9 @@ int nrhs_check_args(int nrhs, int flags) {
                    {CGX_NO_OVERLAP, "CGX_NO_OVERLAP"},   {CGX_DETERMINISTIC, "CGX_DETERMINISTIC"}};
     for (const auto &r : refused)
         if (flags & r.bit)
-            return fail(CGX_ERR_ARG, "cgx_create_nrhs: CGX_F64 (optionally with CGX_TIMING) only, not %s", r.name);
+            return fail(CGX_ERR_ARG, "%s: CGX_F64 (optionally with CGX_TIMING) only, not %s", fn, r.name);
     if (flags & ~CGX_TIMING)
-        return fail(CGX_ERR_ARG, "cgx_create_nrhs: CGX_F64 (optionally with CGX_TIMING) only (flags 0x%x)", flags);
+        return fail(CGX_ERR_ARG, "%s: CGX_F64 (optionally with CGX_TIMING) only (flags 0x%x)", fn, flags);
     return CGX_OK;
 }
 
@@ -63,7 +63,10 @@ int nrhs_alloc(cgx_ctx *c, int nrhs) {
     HIPT(hipMemsetAsync(nr->ws.tickets, 0, kNrhsTickets * sizeof(unsigned), s.stream));
     const size_t xb = (size_t)nrhs * (size_t)c->n * 8;
     if (xb <= kXStageMax) HIPT(hipHostMalloc(reinterpret_cast<void **>(&nr->h_v), xb, hipHostMallocDefault));
-    nr->plan = plan_matvec_nrhs(s.dev, s.nloc, nrhs_width(nrhs), 0, 0, -1, 0, c->lda);
+    if (c->op == OP_CSR)  // cgx_set_csr plans again for the matrix it gets
+        nr->plan = plan_spmm_csr(s.dev, s.nloc, c->csr_cap, nrhs_width(nrhs));
+    else
+        nr->plan = plan_matvec_nrhs(s.dev, s.nloc, nrhs_width(nrhs), 0, 0, -1, 0, c->lda);
     HIPT(hipStreamSynchronize(s.stream));
     return CGX_OK;
 }
@@ -160,9 +163,17 @@ static int nrhs_matvec(cgx_ctx *c, const char *vec, bool with_dot, int64_t k, bo
     NrhsState *nr = c->nr;
     Shard &s = c->sh[0];
     TRY(timing_begin(c, s));
-    HIPT(matvec_nrhs_f64(nr->plan, f64(s.A), c->lda, s.nloc, c->lda, nr->nrhs, f64(vec), c->lda, f64(nr->Ap), c->lda,
-                         with_dot ? f64(vec) : nullptr, c->lda, with_dot ? &nr->sc->pap[ring(k)][0] : nullptr, nr->ws,
-                         s.stream, gated ? &nr->sc->alldone : nullptr));
+    const double *pown = with_dot ? f64(vec) : nullptr;
+    double *dots = with_dot ? &nr->sc->pap[ring(k)][0] : nullptr;
+    const int64_t *gate = gated ? &nr->sc->alldone : nullptr;
+    if (c->op == OP_CSR) {  // the indices were checked on the host before they were uploaded (cgx_set_csr)
+        HIPT(spmm_csr_f64(nr->plan, reinterpret_cast<const int64_t *>(s.csr_rp),
+                          reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), s.nloc, nr->nrhs, f64(vec), c->lda,
+                          f64(nr->Ap), c->lda, pown, c->lda, dots, nr->ws, s.stream, gate));
+    } else {
+        HIPT(matvec_nrhs_f64(nr->plan, f64(s.A), c->lda, s.nloc, c->lda, nr->nrhs, f64(vec), c->lda, f64(nr->Ap), c->lda,
+                             pown, c->lda, dots, nr->ws, s.stream, gate));
+    }
     TRY(timing_end(c, s));
     return CGX_OK;
 }
@@ -306,6 +317,17 @@ int nrhs_get_stats(cgx_ctx *c, cgx_stats *st) {
 int nrhs_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
     NrhsState *nr = c->nr;
     const int K = nrhs_width(nr->nrhs);
+    if (c->op == OP_CSR) {  // cgx_create_csr_nrhs: csr_set_plan's rule
+        const bool r_ok = R == 1 || R == 2 || R == 4 || R == 8 || R == 16 || R == 32;
+        if (!r_ok || U != 1 || !spmm_csr_plan_ok(K, 64 / R, nt))
+            return fail(CGX_ERR_ARG, "cgx_create_csr_nrhs context: rows_per_wave (64 / T) must be 1, 2, 4, 8, 16 or 32, "
+                                     "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
+        TRY(set_dev(c->sh[0]));
+        nr->plan = plan_spmm_csr(c->sh[0].dev, c->sh[0].nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, K, 64 / R, nt,
+                                 blocks_per_cu);
+        c->csr_plan_user = true;
+        return CGX_OK;
+    }
     if (!matvec_nrhs_plan_ok(K, R, U, nt))
         return fail(CGX_ERR_ARG, "an nrhs context of width %d: (rows_per_wave, chunks_in_flight) must be one of %s and "
                                  "the load policy 2 or 8 (got %d, %d, %d)",
@@ -342,6 +364,7 @@ int cgx_residual_norms(cgx_ctx *c, double *rnorm, double *bnorm) {
     const Range range_("cgx_residual_norms");
     if (!c) return fail(CGX_ERR_ARG, "ctx is NULL");
     if (!c->nr) return cgx_residual_norm(c, rnorm, bnorm);
+    TRY(csr_need_matrix(c, "cgx_residual_norms"));
     TRY(check_x_complete(c));
     NrhsState *nr = c->nr;
     Shard &s = c->sh[0];

@@ -26,7 +26,7 @@ int alloc_shard(cgx_ctx *c, Shard &s) {
         else if (c->flags & CGX_SYMMETRIC) set |= PL_SYMV;
         else if (a32(c)) set |= PL_MATVEC_A32;
         else set |= PL_MATVEC;
-        if (c->nr) set |= PL_MATVEC_NRHS;
+        if (c->nr) set |= PL_MATVEC_NRHS | (c->op == OP_CSR ? PL_SPMM : 0);
         HIPT(preload_kernels(set));
     }
     const size_t es = (size_t)c->es;
@@ -704,6 +704,36 @@ int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags)
     TRY(check_device(device));
     cgx_ctx *c = new_ctx_op(OP_CSR, n, 0, 1, flags);
     if (!c) return fail(CGX_ERR_NOMEM, "host allocation failed");
+    c->csr_cap = nnz;
+    c->mode = M_SINGLE;
+    c->sh.resize(1);
+    c->sh[0].dev = device;
+    c->sh[0].index = 0;
+    c->sh[0].row0 = 0;
+    c->sh[0].nloc = n;
+    return finish_create(c, ctx);
+}
+
+// nrhs systems on one CSR matrix (cgx_nrhs.hip, cgx_spmm.hip): a cgx_create_csr
+// context whose vectors, scalars and iteration are a cgx_create_nrhs
+// context's.  The arguments are checked before any device is touched.
+int cgx_create_csr_nrhs(cgx_ctx **ctx, int64_t n, int64_t nnz, int nrhs, int device, int flags) {
+    if (!ctx) return fail(CGX_ERR_ARG, "cgx_create_csr_nrhs: ctx is NULL");
+    *ctx = nullptr;
+    if (n < 1) return fail(CGX_ERR_ARG, "cgx_create_csr_nrhs: n must be >= 1 (got %lld)", (long long)n);
+    if (nnz < 0) return fail(CGX_ERR_ARG, "cgx_create_csr_nrhs: nnz must be >= 0 (got %lld)", (long long)nnz);
+    if (n > (int64_t)INT32_MAX)
+        return fail(CGX_ERR_ARG, "cgx_create_csr_nrhs: n must be below 2^31, col_idx is int32 (got %lld)", (long long)n);
+    TRY(nrhs_check_args(nrhs, flags, "cgx_create_csr_nrhs"));
+    TRY(check_device(device));
+    cgx_ctx *c = new_ctx_op(OP_CSR, n, 0, 1, flags);
+    if (!c) return fail(CGX_ERR_NOMEM, "host allocation failed");
+    c->nr = new (std::nothrow) NrhsState();
+    if (!c->nr) {
+        delete c;
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    c->nr->nrhs = nrhs;
     c->csr_cap = nnz;
     c->mode = M_SINGLE;
     c->sh.resize(1);

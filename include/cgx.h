@@ -154,6 +154,34 @@
  *       r.r bit for bit on the same plan; so does minv == a power of two
  *       (alpha absorbs the factor, p carries it).
  *     - cgx_get_info: flags carries CGX_PRECOND_ACTIVE while a kind is set.
+ *   - Several right-hand sides (cgx_create_csr_nrhs): nrhs (1..CGX_MAX_NRHS)
+ *     systems A x_j = b_j on one CSR matrix, the CSR arrays read once per
+ *     iteration (k_spmm_csr_f64).  The context is a cgx_create_csr context's
+ *     matrix with a cgx_create_nrhs context's vectors, scalars and loop.
+ *     - Order per column: exactly the one above at the same T.  Column j of a
+ *       product is cgx_spmv_csr's result on column j bit for bit; it does not
+ *       depend on the width K (nrhs rounded up to 2, 4 or 8), the load policy
+ *       or the grid.
+ *     - Layout: b and x hold nrhs * n values, system after system; on the
+ *       device column j starts at j * lda doubles (cgx_info.lda).  Values and
+ *       col_idx are loaded once per entry and multiplied by K gathered vector
+ *       elements; columns nrhs..K-1 read column 0 again and are not stored.
+ *     - Freeze and stats as "Several right-hand sides" above: each column has
+ *       its own alpha, beta and stopping point, a stopped column is frozen,
+ *       cgx_get_stats / cgx_get_stats_rhs / cgx_residual_norms report as on a
+ *       cgx_create_nrhs context.  Three launches per iteration in every host
+ *       form; x the same bits across the forms for a given plan.
+ *     - Plans: cgx_set_matvec_plan as on a cgx_create_csr context
+ *       (rows_per_wave = 64 / T, chunks_in_flight = 1, policy 2 or 8); the
+ *       default T follows the mean row length.  cgx_set_csr plans again
+ *       unless the caller chose a plan.
+ *     - Refusals: at creation nrhs outside [1, CGX_MAX_NRHS], n < 1,
+ *       n >= 2^31, nnz < 0 or any flag bit but CGX_TIMING (CGX_ERR_ARG, *ctx
+ *       NULL, before the device is touched); cgx_generate_spd, a non-NULL A,
+ *       cgx_residual_norm, cgx_set_precond and cgx_set_precond_diag
+ *       (CGX_ERR_ARG: batched CG has no preconditioned update kernels);
+ *       cgx_solve_begin, cgx_solve and cgx_residual_norms before the first
+ *       cgx_set_csr (CGX_ERR_STATE).
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -178,7 +206,8 @@ extern "C" {
                            existing call changes meaning, so the version stays); likewise
                            cgx_create_csr and its entry points, and the reported bit
                            CGX_CSR_ACTIVE; likewise cgx_set_precond and its entry points,
-                           and the reported bit CGX_PRECOND_ACTIVE */
+                           and the reported bit CGX_PRECOND_ACTIVE; likewise
+                           cgx_create_csr_nrhs and cgx_spmm_csr (new functions only, no new bit) */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -505,6 +534,10 @@ int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags)
 /* Host arrays (row_ptr[n] entries, at most the context's nnz); runs cgx_csr_check first and
  * uploads nothing when it fails (an earlier matrix stays as it was).  Ends a solve in progress. */
 int cgx_set_csr(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, const double *values);
+/* One GPU, fp64: nrhs (1..CGX_MAX_NRHS) systems A x_j = b_j on one CSR matrix with room for
+ * nnz entries, solved together, one read of the CSR arrays per iteration.
+ * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
+int cgx_create_csr_nrhs(cgx_ctx **ctx, int64_t n, int64_t nnz, int nrhs, int device, int flags);
 
 /* ---- diagonal preconditioning of a cgx_create_csr context (see "Sparse A" above) ------------- */
 #define CGX_PC_NONE   0
@@ -625,6 +658,13 @@ int cgx_matvec_nrhs(const void *A, int64_t lda, int64_t rows, int64_t cols, int 
  * T comes from CGX_SPMV_PLAN="T=..,nt=..,bpc=.." (default T = 8). */
 int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
                  const void *values, const void *v, void *out, void *stream);
+/* Kernel-level, device pointers: Out[j*ldo + i] = sum_e values[e] * V[j*ldv + col_idx[e]],
+ * j < nrhs.  Column j is cgx_spmv_csr's result on column j bit for bit at the same T.
+ * The indices must have passed cgx_csr_check.  T comes from
+ * CGX_SPMM_PLAN="T=..,nt=..,bpc=.." (default T = 8). */
+int cgx_spmm_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
+                 const void *values, int nrhs, const void *V, int64_t ldv,
+                 void *Out, int64_t ldo, void *stream);
 /* vecVec: *out_dev = a . b */
 int cgx_dot(int dtype, int64_t n, const void *a, const void *b, void *out_dev, void *stream);
 /* residual x2 + vecVec: r = b - Ax; p = b - Ax; *rr_dev = r.r (rr_dev may be NULL) */
