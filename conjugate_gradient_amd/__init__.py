@@ -39,7 +39,7 @@ __all__ = [
     "device_pci_bus_id", "device_link",
     "CGX_MAX_NRHS", "matVec_nrhs",
     "CGX_CSR_ACTIVE", "spmv_csr", "spmm_csr",
-    "CGX_PRECOND_ACTIVE", "PRECOND_KINDS",
+    "CGX_PRECOND_ACTIVE", "PRECOND_KINDS", "PC_BLOCK", "CGX_MAX_PC_BLOCK", "csr_diag_blocks", "precond_block_invert",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
     "count_text", "read_dims", "device_count", "get_unique_id", "DeviceArray",
 ]
@@ -71,6 +71,11 @@ CGX_PRECOND_ACTIVE = 0x10000000  # reported in info.flags: a CSR context iterati
 # cgx_set_precond's kinds, CGX_PC_NONE / CGX_PC_JACOBI / CGX_PC_DIAG (include/cgx.h), by the names Solver.precond
 # reports.  Kept out of the CGX_* names: those are the flag words, and a kind is not a bit of one.
 PRECOND_KINDS = {"none": 0, "jacobi": 1, "diag": 2}
+# CGX_PC_BLOCK, the block-Jacobi kind: it has its own entry points (Solver.set_precond_block), so it stays out of the
+# dict of kinds cgx_set_precond knows, and, a kind and not a flag bit, out of the CGX_* names; Solver.precond reports
+# it as "block".
+PC_BLOCK = 3
+CGX_MAX_PC_BLOCK = 8  # the largest block size
 CGX_MAX_NRHS = 8  # cgx_create_nrhs: systems solved together on one matrix
 
 # cgx_phase_times indices (include/cgx.h), in the order the phases tile an iteration
@@ -188,6 +193,12 @@ def lib() -> ctypes.CDLL:
         "cgx_set_precond_diag": ([vp, vp], i32),
         "cgx_get_precond": ([vp, ctypes.POINTER(i32)], i32),
         "cgx_get_precond_diag": ([vp, vp], i32),
+        "cgx_set_precond_block": ([vp, i32], i32),
+        "cgx_set_precond_block_values": ([vp, i32, vp], i32),
+        "cgx_get_precond_block": ([vp, ctypes.POINTER(i32), vp], i32),
+        "cgx_precond_block_invert": ([i64, i32, vp, vp], i32),
+        "cgx_precond_block_check": ([i64, i32, vp], i32),
+        "cgx_csr_diag_blocks": ([i64, i32, vp, vp, vp, vp, vp], i32),
         "cgx_get_unique_id": ([ctypes.POINTER(UniqueId)], i32),
         "cgx_rccl_available": ([], i32),
         "cgx_create_rank": ([pctx, i64, i32, i32, ctypes.POINTER(UniqueId), i32, i32], i32),
@@ -486,6 +497,48 @@ def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int,
             d.free()
 
 
+def _block_count(n: int, bs: int) -> int:
+    return (n + bs - 1) // bs
+
+
+def csr_diag_blocks(indptr, indices, data, bs: int) -> np.ndarray:
+    """A's ``bs x bs`` diagonal blocks, extracted on the device (k_csr_diag_blocks): an
+    ``(nblk, bs, bs)`` array, each entry the sum from +0.0 in stored order of the row's entries in
+    that column, +0.0 where there is none.  The structure is checked on the host first."""
+    rp, ci, va = _csr_arrays(indptr, indices, data)
+    n = rp.size - 1
+    _need(n >= 1, "csr_diag_blocks: indptr needs n + 1 >= 2 entries")
+    _need(isinstance(bs, (int, np.integer)) and 2 <= bs <= CGX_MAX_PC_BLOCK,
+          f"csr_diag_blocks: bs must be in [2, {CGX_MAX_PC_BLOCK}] (got {bs})")
+    L = lib()
+    _csr_checked("csr_diag_blocks", rp, ci, n, n)
+    nblk = _block_count(n, int(bs))
+    d_rp, d_ci, d_va = DeviceArray.from_host(rp), DeviceArray.from_host(ci), DeviceArray.from_host(va)
+    d_D = DeviceArray(nblk * bs * bs)
+    try:
+        _check(L.cgx_csr_diag_blocks(n, int(bs), d_rp.ptr, d_ci.ptr, d_va.ptr, d_D.ptr, None), "cgx_csr_diag_blocks")
+        return d_D.to_host().reshape(nblk, bs, bs)
+    finally:
+        for d in (d_rp, d_ci, d_va, d_D):
+            d.free()
+
+
+def precond_block_invert(D: np.ndarray, n: int) -> np.ndarray:
+    """cgx_precond_block_invert (host only): the inverses of the ``(nblk, bs, bs)`` diagonal blocks
+    of an n-row matrix, by Cholesky from each block's lower triangle; symmetric bit for bit.
+    CgxError(-4) names the lowest block with a pivot that is not finite or not > 0."""
+    D = np.asarray(D)
+    _need(D.dtype == np.float64 and D.ndim == 3 and D.shape[1] == D.shape[2],
+          f"precond_block_invert: float64 blocks of shape (nblk, bs, bs) needed (got {D.dtype}, {D.shape})")
+    bs = D.shape[1]
+    _need(n >= 1 and D.shape[0] == _block_count(n, max(bs, 1)),
+          f"precond_block_invert: {D.shape[0]} blocks of {bs} rows do not cover n = {n}")
+    W = np.empty_like(D, order="C")
+    _check(lib().cgx_precond_block_invert(int(n), int(bs), _ptr(np.ascontiguousarray(D)), _ptr(W)),
+           "cgx_precond_block_invert")
+    return W
+
+
 def vecVec(a: DeviceArray, b: DeviceArray, out: DeviceArray, n: int | None = None) -> None:
     """serialConjugate.c:145-155: out[0] = a . b (device scalar)."""
     n = n if n is not None else a.count
@@ -625,7 +678,7 @@ class Solver:
     def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64,
                  precond=None, nrhs: int | None = None) -> "Solver":
         """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)
-        and, with ``precond`` ("jacobi" or an array), its preconditioner (:meth:`set_precond`).
+        and, with ``precond`` ("jacobi", an array or ``("block", bs)``), its preconditioner (:meth:`set_precond`).
         ``nrhs=K``: K systems on the matrix solved together (:meth:`csr`; no preconditioner)."""
         rp, ci, va = _csr_arrays(indptr, indices, data)
         _need(rp.size >= 2, "from_csr: indptr needs n + 1 >= 2 entries")
@@ -655,10 +708,13 @@ class Solver:
         taken from the matrix on the device; CgxError(-4) names the lowest row whose
         diagonal is missing, not finite or not > 0, and nothing changes), ``None``
         (off), or an array of n positive float64 values (cgx_set_precond_diag).
+        ``("block", bs)`` is :meth:`set_precond_block` with that block size.
         Ends a solve in progress; :meth:`set_csr` turns it off again."""
         L = lib()
         if precond is None:
             _check(L.cgx_set_precond(self._h, PRECOND_KINDS["none"]), "cgx_set_precond")
+        elif isinstance(precond, tuple) and len(precond) == 2 and precond[0] == "block":
+            self.set_precond_block(precond[1])  # ("block", bs): block Jacobi
         elif isinstance(precond, str):
             _need(precond == "jacobi", f'set_precond: "jacobi", None or an array (got {precond!r})')
             _check(L.cgx_set_precond(self._h, PRECOND_KINDS["jacobi"]), "cgx_set_precond")
@@ -670,16 +726,51 @@ class Solver:
 
     @property
     def precond(self) -> str:
-        """"none", "jacobi" or "diag" ("none" on every solver that is not a CSR one)."""
+        """"none", "jacobi", "diag" or "block" ("none" on every solver that is not a CSR one)."""
         k = ctypes.c_int(0)
         _check(lib().cgx_get_precond(self._h, ctypes.byref(k)), "cgx_get_precond")
+        if k.value == PC_BLOCK:
+            return "block"
         return next(name for name, kind in PRECOND_KINDS.items() if kind == k.value)
 
     def precond_diag(self) -> np.ndarray:
-        """The n values of M^-1 in use (CgxError(-6) when preconditioning is off)."""
+        """The n values of M^-1 in use (CgxError(-6) when preconditioning is off or block Jacobi)."""
         out = np.empty(self.n, np.float64)
         _check(lib().cgx_get_precond_diag(self._h, _ptr(out)), "cgx_get_precond_diag")
         return out
+
+    def set_precond_block(self, bs: int, values=None) -> None:
+        """Block-Jacobi preconditioning of a ``csr_nnz`` solver: M^-1 = the inverses of the
+        matrix's ``bs x bs`` diagonal blocks (2 <= bs <= 8; the last block is smaller when bs does
+        not divide n), extracted on the device and inverted on the host by Cholesky.  CgxError(-4)
+        names the lowest block that is not positive definite, and nothing changes.  ``values``: the
+        caller's inverse blocks instead, float64 of shape (ceil(n / bs), bs, bs); they are checked
+        (finite, diagonal > 0), their symmetry and definiteness are the caller's business.
+        Ends a solve in progress; :meth:`set_csr` turns it off again."""
+        _need(isinstance(bs, (int, np.integer)) and not isinstance(bs, bool),
+              f"set_precond_block: bs must be an integer (got {bs!r})")
+        L = lib()
+        if values is None:
+            _check(L.cgx_set_precond_block(self._h, int(bs)), "cgx_set_precond_block")
+            return
+        w = np.asarray(values)
+        _need(w.dtype == np.float64, f"set_precond_block: the values must be float64 (got {w.dtype})")
+        if 2 <= bs <= CGX_MAX_PC_BLOCK:  # any other bs: the library refuses it before it reads the values
+            shape = (_block_count(self.n, int(bs)), int(bs), int(bs))
+            _need(w.shape == shape, f"set_precond_block: values of shape {w.shape}, {shape} needed")
+        _check(L.cgx_set_precond_block_values(self._h, int(bs), _ptr(np.ascontiguousarray(w))),
+               "cgx_set_precond_block_values")
+
+    @property
+    def precond_block(self) -> tuple:
+        """(bs, W): the block size and the (nblk, bs, bs) inverse blocks in use; the unused rows
+        and columns of a short last block are +0.0 (CgxError(-6) unless :attr:`precond` is "block")."""
+        L = lib()
+        b = ctypes.c_int(0)
+        _check(L.cgx_get_precond_block(self._h, ctypes.byref(b), None), "cgx_get_precond_block")
+        W = np.empty((_block_count(self.n, b.value), b.value, b.value), np.float64)
+        _check(L.cgx_get_precond_block(self._h, ctypes.byref(b), _ptr(W)), "cgx_get_precond_block")
+        return b.value, W
 
     def _vshape(self, rows: int | None = None) -> tuple:
         """The shape of a b or x argument: (n,), or (nrhs, n) on an nrhs context."""

@@ -40,7 +40,10 @@
  * entries that are not +-0 are kept, compressed to CSR row block by row block
  * as they are parsed, and the solve runs through a cgx_create_csr context;
  * --stats adds "nnz: <count>"); with it --jacobi (cgx_set_precond: the
- * solve is preconditioned with 1 / diag(A); --stats adds "precond: jacobi").
+ * solve is preconditioned with 1 / diag(A); --stats adds "precond: jacobi")
+ * or --block-jacobi BS (cgx_set_precond_block: preconditioned with the
+ * inverses of A's BS x BS diagonal blocks, 2 <= BS <= 8; --stats adds
+ * "precond: block-jacobi BS").
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -122,8 +125,9 @@ static void usage(const char *prog) {
             "          [--threads T] [--print-x] [--stats] matrixA vectorb initialguess\n"
             "       %s --spd N [--seed S] [--gpus P] [--a-fp32] [--eps E] [--max-iter M] [--stats]\n"
             "       %s --nrhs K ... (one GPU, fp64: K systems on one matrix; vectorb and initialguess hold K*N values)\n"
-            "       %s --csr [--jacobi] ... (one GPU, fp64: the matrix's non-zero entries only, solved as a sparse CSR\n"
-            "          system; --jacobi: preconditioned with 1 / diag(A))\n",
+            "       %s --csr [--jacobi | --block-jacobi BS] ... (one GPU, fp64: the matrix's non-zero entries only, solved\n"
+            "          as a sparse CSR system; --jacobi: preconditioned with 1 / diag(A); --block-jacobi BS: with the\n"
+            "          inverses of A's BS x BS diagonal blocks, BS in 2..8)\n",
             prog, prog, prog, prog);
 }
 
@@ -331,7 +335,7 @@ int main(int argc, char **argv) {
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
-    long long max_iter = -1, n_opt = -1, spd_n = -1, nrhs = 0;
+    long long max_iter = -1, n_opt = -1, spd_n = -1, nrhs = 0, block_bs = 0; /* block_bs > 0: --block-jacobi */
     unsigned long long seed = 42;
     const char *dims_path = NULL;
     const char *pos[3];
@@ -350,7 +354,13 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "--p2p")) p2p = 1;
         else if (!strcmp(a, "--csr")) csr = 1;
         else if (!strcmp(a, "--jacobi")) jacobi = 1;
-        else if (!strcmp(a, "--eps") && has_val) {
+        else if (!strcmp(a, "--block-jacobi")) {
+            if (has_val && !opt_ll(a, argv[++i], &block_bs)) return 2;
+            if (!has_val || block_bs < 2 || block_bs > CGX_MAX_PC_BLOCK) {
+                fprintf(stderr, "--block-jacobi must be an integer in [2, %d]\n", CGX_MAX_PC_BLOCK);
+                return 2;
+            }
+        } else if (!strcmp(a, "--eps") && has_val) {
             if (!opt_double(a, argv[++i], &eps)) return 2;
         } else if (!strcmp(a, "--max-iter") && has_val) {
             if (!opt_ll(a, argv[++i], &max_iter)) return 2;
@@ -400,6 +410,14 @@ int main(int argc, char **argv) {
     }
     if (jacobi && (!csr || fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
         fprintf(stderr, "--jacobi preconditions a --csr solve (fp64 on one GPU from a matrix file: no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
+        return 2;
+    }
+    if (block_bs > 0 && jacobi) {
+        fprintf(stderr, "--block-jacobi and --jacobi are two preconditioners: give one\n");
+        return 2;
+    }
+    if (block_bs > 0 && (!csr || fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
+        fprintf(stderr, "--block-jacobi preconditions a --csr solve (fp64 on one GPU from a matrix file: no --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
         return 2;
     }
     if (csr && (fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
@@ -627,6 +645,10 @@ int main(int argc, char **argv) {
             rc = cgx_set_precond(ctx, CGX_PC_JACOBI);
             if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond");
         }
+        if (block_bs > 0) { /* the diagonal blocks of the uploaded matrix; one it cannot invert ends the run */
+            rc = cgx_set_precond_block(ctx, (int)block_bs);
+            if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond_block");
+        }
         rc = cgx_set_rows(ctx, 0, n, NULL, n, b, x);
         t_dist1 = now_s();
         free(b);
@@ -681,6 +703,7 @@ int main(int argc, char **argv) {
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
     if (stats && csr) printf("nnz: %lld\n", (long long)csrm.nnz);
     if (stats && jacobi) printf("precond: jacobi\n");
+    if (stats && block_bs > 0) printf("precond: block-jacobi %lld\n", block_bs);
     if (stats && nrhs > 0)
         for (int j = 0; j < (int)nrhs; ++j) {
             cgx_stats sj;

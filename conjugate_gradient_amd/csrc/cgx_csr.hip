@@ -10,6 +10,10 @@
 // cgx_set_precond / cgx_set_precond_diag put n positive values minv on the
 // device (1 / diag(A) extracted there, or the caller's); while they are set,
 // do_begin and the two update launches run the PCG kernels (cgx_pcg.hip).
+// cgx_set_precond_block / cgx_set_precond_block_values put the inverses W of
+// A's bs x bs diagonal blocks there instead (extracted on the device, inverted
+// on the host by cgx_pcblock.hip, or the caller's), and one more n-vector z;
+// the iteration then runs cgx_pcg_block.hip's kernels.
 #include "cgx_ctx.h"
 
 namespace cgxh {
@@ -32,10 +36,24 @@ int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
     return CGX_OK;
 }
 
+// The block kind's W goes (z stays with the context: free_shard); the stream is idle.
+static int pc_block_free(cgx_ctx *c) {
+    Shard &s = c->sh[0];
+    c->pc_bs = 0;
+    if (s.pc_w) {
+        TRY(set_dev(s));
+        HIPT(hipFree(s.pc_w));
+        s.pc_w = nullptr;
+        s.pc_wld = 0;
+    }
+    return CGX_OK;
+}
+
 // The preconditioner's buffer goes (cgx_set_csr, cgx_set_precond(CGX_PC_NONE)); the stream is idle.
 static int pc_drop(cgx_ctx *c) {
     Shard &s = c->sh[0];
     c->pc_kind = CGX_PC_NONE;
+    TRY(pc_block_free(c));
     if (s.pc_minv) {
         TRY(set_dev(s));
         HIPT(hipFree(s.pc_minv));
@@ -44,15 +62,21 @@ static int pc_drop(cgx_ctx *c) {
     return CGX_OK;
 }
 
-// What every call that sets a preconditioner checks first.
-static int pc_need_csr(const cgx_ctx *c, const char *what) {
+// What every call that sets a preconditioner checks first: the context's kind ...
+static int pc_need_ctx(const cgx_ctx *c, const char *what) {
     if (!c) return fail(CGX_ERR_ARG, "%s: ctx is NULL", what);
     if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "%s: not a cgx_create_csr context", what);
     // OP_CSR alone does not do: the K-column update kernels have no PCG form
     if (c->nr) return fail(CGX_ERR_ARG, "%s: not with several right-hand sides (a cgx_create_csr_nrhs context)", what);
+    return CGX_OK;
+}
+// ... and that it has a matrix.
+static int pc_need_csr(const cgx_ctx *c, const char *what) {
+    TRY(pc_need_ctx(c, what));
     return csr_need_matrix(c, what);
 }
 
+// room for n doubles
 static int pc_alloc(const Shard &s, int64_t n, char **out) {
     const hipError_t e = hipMalloc(out, (size_t)n * 8);
     if (e != hipSuccess)
@@ -96,6 +120,53 @@ static int pc_jacobi(cgx_ctx *c) {
     if (s.pc_minv) HIPT(hipFree(s.pc_minv));
     s.pc_minv = fresh;
     c->pc_kind = CGX_PC_JACOBI;
+    c->state = ST_IDLE;
+    return pc_block_free(c);
+}
+
+static int pc_block_args(const cgx_ctx *c, int bs, const char *what) {
+    TRY(pc_need_ctx(c, what));
+    if (bs == 1)
+        return fail(CGX_ERR_ARG, "%s: bs = 1 is point Jacobi: use cgx_set_precond(ctx, CGX_PC_JACOBI)", what);
+    if (bs < 2 || bs > CGX_MAX_PC_BLOCK)
+        return fail(CGX_ERR_ARG, "%s: bs must be in [2, %d] (got %d)", what, CGX_MAX_PC_BLOCK, bs);
+    return CGX_OK;
+}
+
+// CGX_PC_BLOCK from inverse blocks in the host layout (checked by the caller;
+// the stream is idle): W goes up in the kernels' layout into a fresh buffer,
+// which replaces the context's preconditioner only when everything before
+// went well.
+static int pc_block_install(cgx_ctx *c, int bs, const double *W) {
+    Shard &s = c->sh[0];
+    const int64_t n = c->n, nblk = (n + bs - 1) / bs, wld = round_up(nblk, 2);
+    std::vector<double> dev;
+    try {
+        dev.assign((size_t)(bs * bs) * (size_t)wld, 0.0);
+    } catch (const std::bad_alloc &) {
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    for (int64_t k = 0; k < nblk; ++k) {
+        const int t = (int)std::min<int64_t>(bs, n - k * bs);  // the unused slots of a short block stay +0.0
+        for (int i = 0; i < t; ++i)
+            for (int j = 0; j < t; ++j) dev[(size_t)(i * bs + j) * wld + k] = W[k * bs * bs + i * bs + j];
+    }
+    TRY(set_dev(s));
+    HIPT(preload_kernels(PL_PCG_BLOCK));
+    if (!s.pc_z) TRY(pc_alloc(s, n, &s.pc_z));
+    char *fresh = nullptr;
+    TRY(pc_alloc(s, (int64_t)dev.size(), &fresh));
+    hipError_t e = hipMemcpyAsync(fresh, dev.data(), dev.size() * 8, hipMemcpyHostToDevice, s.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
+    if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        return fail(CGX_ERR_HIP, "the upload of the inverse blocks: %s", hipGetErrorString(e));
+    }
+    TRY(pc_drop(c));  // the diagonal kinds' values, or the earlier blocks
+    s.pc_w = fresh;
+    s.pc_wld = wld;
+    c->pc_bs = bs;
+    c->pc_kind = CGX_PC_BLOCK;
     c->state = ST_IDLE;
     return CGX_OK;
 }
@@ -142,6 +213,77 @@ int cgx_set_precond_diag(cgx_ctx *c, const double *minv) {
     HIPT(hipStreamSynchronize(s.stream));
     c->pc_kind = CGX_PC_DIAG;
     c->state = ST_IDLE;
+    return pc_block_free(c);
+}
+
+int cgx_set_precond_block(cgx_ctx *c, int bs) {
+    const Range range_("cgx_set_precond_block");
+    TRY(pc_block_args(c, bs, "cgx_set_precond_block"));
+    TRY(csr_need_matrix(c, "cgx_set_precond_block"));
+    Shard &s = c->sh[0];
+    const int64_t nblk = (c->n + bs - 1) / bs;
+    const size_t cnt = (size_t)nblk * bs * bs;
+    std::vector<double> D, W;
+    try {
+        D.resize(cnt);
+        W.resize(cnt);
+    } catch (const std::bad_alloc &) {
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    TRY(sync_all(c));
+    TRY(set_dev(s));
+    HIPT(preload_kernels(PL_PCG_BLOCK));
+    char *dD = nullptr;
+    TRY(pc_alloc(s, (int64_t)cnt, &dD));
+    auto extract = [&]() -> int {
+        HIPT(csr_diag_blocks_f64(c->n, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                 reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(dD), s.stream));
+        HIPT(hipMemcpyAsync(D.data(), dD, cnt * 8, hipMemcpyDeviceToHost, s.stream));
+        HIPT(hipStreamSynchronize(s.stream));
+        return CGX_OK;
+    };
+    const int rc = extract();
+    (void)hipFree(dD);
+    TRY(rc);
+    // nothing has changed yet: a block that is not positive definite leaves the context as it was
+    TRY(cgx_precond_block_invert(c->n, bs, D.data(), W.data()));
+    TRY(cgx_precond_block_check(c->n, bs, W.data()));  // an inverse that overflowed
+    return pc_block_install(c, bs, W.data());
+}
+
+int cgx_set_precond_block_values(cgx_ctx *c, int bs, const double *W) {
+    const Range range_("cgx_set_precond_block_values");
+    TRY(pc_block_args(c, bs, "cgx_set_precond_block_values"));
+    if (!W) return fail(CGX_ERR_ARG, "cgx_set_precond_block_values: W is NULL");
+    TRY(csr_need_matrix(c, "cgx_set_precond_block_values"));
+    TRY(cgx_precond_block_check(c->n, bs, W));  // nothing changes when it fails
+    TRY(sync_all(c));
+    return pc_block_install(c, bs, W);
+}
+
+int cgx_get_precond_block(cgx_ctx *c, int *bs, double *W) {
+    if (!c || !bs) return fail(CGX_ERR_ARG, "cgx_get_precond_block: NULL argument");
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_get_precond_block: not a cgx_create_csr context");
+    if (c->pc_kind != CGX_PC_BLOCK)
+        return fail(CGX_ERR_STATE, "cgx_get_precond_block: the preconditioner is not CGX_PC_BLOCK");
+    const int b = c->pc_bs;
+    if (W) {
+        Shard &s = c->sh[0];
+        const int64_t n = c->n, nblk = (n + b - 1) / b, wld = s.pc_wld;
+        std::vector<double> dev;
+        try {
+            dev.resize((size_t)(b * b) * (size_t)wld);
+        } catch (const std::bad_alloc &) {
+            return fail(CGX_ERR_NOMEM, "host allocation failed");
+        }
+        TRY(set_dev(s));
+        HIPT(hipMemcpyAsync(dev.data(), s.pc_w, dev.size() * 8, hipMemcpyDeviceToHost, s.stream));
+        HIPT(hipStreamSynchronize(s.stream));
+        for (int64_t k = 0; k < nblk; ++k)
+            for (int i = 0; i < b; ++i)
+                for (int j = 0; j < b; ++j) W[k * b * b + i * b + j] = dev[(size_t)(i * b + j) * wld + k];
+    }
+    *bs = b;
     return CGX_OK;
 }
 
@@ -155,6 +297,8 @@ int cgx_get_precond_diag(cgx_ctx *c, double *minv) {
     if (!c || !minv) return fail(CGX_ERR_ARG, "cgx_get_precond_diag: NULL argument");
     if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_get_precond_diag: not a cgx_create_csr context");
     if (c->pc_kind == CGX_PC_NONE) return fail(CGX_ERR_STATE, "cgx_get_precond_diag: no preconditioner is set");
+    if (c->pc_kind == CGX_PC_BLOCK)
+        return fail(CGX_ERR_STATE, "cgx_get_precond_diag: the preconditioner is CGX_PC_BLOCK (cgx_get_precond_block)");
     Shard &s = c->sh[0];
     TRY(set_dev(s));
     HIPT(hipMemcpyAsync(minv, s.pc_minv, (size_t)c->n * 8, hipMemcpyDeviceToHost, s.stream));
@@ -225,6 +369,18 @@ int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *co
     HIPT(spmv_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
                       static_cast<const double *>(values), rows, static_cast<const double *>(v),
                       static_cast<double *>(out), nullptr, nullptr, ws, static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
+int cgx_csr_diag_blocks(int64_t n, int bs, const void *row_ptr, const void *col_idx, const void *values, void *D,
+                        void *stream) {
+    if (n < 1) return fail(CGX_ERR_SHAPE, "cgx_csr_diag_blocks: bad shape");
+    if (bs < 2 || bs > CGX_MAX_PC_BLOCK)
+        return fail(CGX_ERR_ARG, "cgx_csr_diag_blocks: bs must be in [2, %d] (got %d)", CGX_MAX_PC_BLOCK, bs);
+    if (!row_ptr || !col_idx || !values || !D) return fail(CGX_ERR_ARG, "cgx_csr_diag_blocks: NULL pointer");
+    HIPT(csr_diag_blocks_f64(n, bs, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
+                             static_cast<const double *>(values), static_cast<double *>(D),
+                             static_cast<hipStream_t>(stream)));
     return CGX_OK;
 }
 

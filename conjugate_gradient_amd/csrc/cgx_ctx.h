@@ -4,7 +4,8 @@
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
 //   cgx_nrhs.hip      cgx_create_nrhs / cgx_create_csr_nrhs contexts: several systems per pass over A
-//   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload), diagonal preconditioning
+//   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload), diagonal and block preconditioning
+//   cgx_pcblock.hip   block Jacobi's host side: the blocks' Cholesky inversion and the check of a caller's blocks
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
 //
@@ -188,7 +189,11 @@ struct Shard {
     char *pown = nullptr;  // this shard's p: pfull + row0 (dense, CSR) or the slab interior (Poisson)
     // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap]); no s.A
     char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
-    char *pc_minv = nullptr;  // ... and the preconditioner's n values (cgx_ctx::pc_kind != CGX_PC_NONE)
+    char *pc_minv = nullptr;  // ... and the preconditioner's n values (cgx_ctx::pc_kind JACOBI or DIAG)
+    // CGX_PC_BLOCK: the inverse blocks, entry (i, j) of block k at pc_w[(i * bs + j) * pc_wld + k], and z = W r
+    // (n doubles, allocated when the kind is first set, kept until the context goes)
+    char *pc_w = nullptr, *pc_z = nullptr;
+    int64_t pc_wld = 0;
     // fused Poisson iteration: r with halo rows (r = rh + one row) and a
     // second p slab; p_k lives in pfull for even k, in p2 for odd k
     char *rh = nullptr, *p2 = nullptr;
@@ -291,6 +296,7 @@ struct cgx_ctx {
     // cgx_set_precond / cgx_set_precond_diag: CGX_PC_NONE, or the iteration runs the PCG kernels on
     // sh[0].pc_minv (cgx_pcg.hip); cgx_set_csr goes back to CGX_PC_NONE
     int pc_kind = CGX_PC_NONE;
+    int pc_bs = 0;     // CGX_PC_BLOCK: the block size, and the iteration runs cgx_pcg_block.hip's kernels on sh[0].pc_w
     int64_t m = 0;     // Poisson grid width (n = m*m)
     int nranks = 1;
     int flags = 0;

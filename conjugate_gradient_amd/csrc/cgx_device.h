@@ -1,6 +1,6 @@
 // cgx_device.h -- internal to libcgx: device and host helpers shared by the
 // kernel files (cgx_matvec.hip, cgx_vector.hip, cgx_poisson.hip,
-// cgx_ref_f32.hip, cgx_symv.hip, cgx_pcg.hip).  Not part of the C ABI (include/cgx.h).
+// cgx_ref_f32.hip, cgx_symv.hip, cgx_pcg.hip, cgx_pcg_block.hip).  Not part of the C ABI (include/cgx.h).
 #pragma once
 
 #include "cgx_kernels.h"

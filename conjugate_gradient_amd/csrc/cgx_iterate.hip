@@ -201,6 +201,11 @@ int do_begin(cgx_ctx *c) {
                                       reinterpret_cast<const float *>(s.Ap), reinterpret_cast<float *>(s.r),
                                       reinterpret_cast<float *>(s.pown), reinterpret_cast<float *>(slot(s, os)),
                                       s.stream, reinterpret_cast<int64_t *>(slot(s, S_KDONE))));
+        } else if (c->pc_kind == CGX_PC_BLOCK) {
+            // block Jacobi: p0 = W r0 block by block, and r0.z0 beside r0.r0
+            HIPT(pcgb_residual_f64(c->pc_bs, s.nloc, f64(s.b), zero ? nullptr : f64(s.Ap), f64(s.pc_w), s.pc_wld,
+                                   f64(s.r), f64(s.pown), slot_f64(s, os), kRzStride, s.ws, s.stream,
+                                   slot_i64(s, S_KDONE)));
         } else if (c->pc_kind != CGX_PC_NONE) {
             // preconditioned: p0 = minv o r0, and r0.z0 beside r0.r0 (one GPU: os is the global slot)
             HIPT(pcg_residual_f64(s.nloc, f64(s.b), zero ? nullptr : f64(s.Ap), f64(s.pc_minv), f64(s.r), f64(s.pown),
@@ -477,6 +482,11 @@ int launch_update_r(const cgx_ctx *c, const Shard &s, int64_t k, bool gated) {
         HIPT(update_xr_dot_ref_f32(s.nloc, f32(s.x), f32(s.r), f32(s.pown), f32(s.Ap), slot_f32(s, rk),
                                    slot_f32(s, pg), slot_f32(s, ro), s.stream, gate_of(s, gated),
                                    c->fuse_f32 ? &ps : nullptr));
+    } else if (c->pc_kind == CGX_PC_BLOCK) {
+        // r -= alpha Ap with alpha = r.z / p.Ap; z = W r stored; r.r and r.z from the one pass
+        HIPT(pcgb_update_r_f64(c->pc_bs, s.nloc, f64(s.r), f64(s.Ap), f64(s.pc_w), s.pc_wld, f64(s.pc_z),
+                               slot_f64(s, rk + kRzStride), slot_f64(s, pg), slot_f64(s, ro), kRzStride, s.ws,
+                               s.stream, gate_of(s, gated)));
     } else if (c->pc_kind != CGX_PC_NONE) {
         // r -= alpha Ap with alpha = r.z / p.Ap; r.r and r.z (z = minv o r) from the one pass
         HIPT(pcg_update_r_f64(s.nloc, f64(s.r), f64(s.Ap), f64(s.pc_minv), slot_f64(s, rk + kRzStride), slot_f64(s, pg),
@@ -508,6 +518,12 @@ int launch_update_xp(const cgx_ctx *c, const Shard &s, int64_t k, XpForm form, d
         const PeerSumF32 ps = fold_rr ? peer_sum_f32(c, s, rl, rg) : PeerSumF32{};
         HIPT(update_p_ref_f32(s.nloc, f32(s.pown), f32(s.r), slot_f32(s, rg), slot_f32(s, rk), s.stream, stop_eps,
                               stop_k, kdone, rrfinal, rec_of(c, s, decide), fold_rr ? &ps : nullptr));
+    } else if (c->pc_kind == CGX_PC_BLOCK) {
+        // x += alpha p; p = z + (r.z_new / r.z_old) p with the z the r update stored; the stop as below
+        HIPT(pcgb_update_xp_f64(s.nloc, f64(s.x), f64(s.pown), f64(s.pc_z), slot_f64(s, rk + kRzStride),
+                                slot_f64(s, pg), form == XP_X_ONLY ? nullptr : slot_f64(s, rg),
+                                slot_f64(s, rg + kRzStride), s.stream, stop_eps, stop_k, kdone, rrfinal,
+                                rec_of(c, s, decide)));
     } else if (c->pc_kind != CGX_PC_NONE) {
         // x += alpha p; p = minv o r + (r.z_new / r.z_old) p; the stop is decided on r.r as below
         HIPT(pcg_update_xp_f64(s.nloc, f64(s.x), f64(s.pown), f64(s.r), f64(s.pc_minv), slot_f64(s, rk + kRzStride),

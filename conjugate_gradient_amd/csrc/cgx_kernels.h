@@ -251,6 +251,33 @@ hipError_t pcg_update_xp_f64(int64_t n, double *x, double *p, const double *r, c
 hipError_t csr_diag_minv_f64(int64_t n, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
                              double *minv, unsigned long long *bad, hipStream_t s);
 
+// ---- block-Jacobi preconditioned CG on CSR contexts (cgx_pcg_block.hip) --------------
+// W = the nblk = ceil(n / bs) inverse diagonal blocks, 2 <= bs <= kMaxPcBlock;
+// entry (i, j) of block k at W[(i * bs + j) * wld + k], wld >= nblk.  z = W r is
+// formed block by block (the order is in cgx.h, "Sparse A") and stored by the r
+// update for the x/p update.  Sums, slots and clear2 as the diagonal kernels'.
+// The vectors are 16-byte aligned (hipErrorInvalidValue otherwise, or a bs
+// outside the range).
+constexpr int kMaxPcBlock = 8;
+// r = b - Ax (Ax == nullptr: b - 0.0); p = W r
+hipError_t pcgb_residual_f64(int bs, int64_t n, const double *b, const double *Ax, const double *W, int64_t wld,
+                             double *r, double *p, double *out, int stride, const RedWs &ws, hipStream_t s,
+                             int64_t *clear2 = nullptr);
+// r -= alpha Ap with alpha = *rz_old / *pAp; z = W r
+hipError_t pcgb_update_r_f64(int bs, int64_t n, double *r, const double *Ap, const double *W, int64_t wld, double *z,
+                             const double *rz_old, const double *pAp, double *out, int stride, const RedWs &ws,
+                             hipStream_t s, const int64_t *gate = nullptr);
+// x += alpha p; then (rr != nullptr) p = z + (*rz_new / *rz_old) p.  The
+// stopping decision is update_xp_f64's, on *rr.
+hipError_t pcgb_update_xp_f64(int64_t n, double *x, double *p, const double *z, const double *rz_old,
+                              const double *pAp, const double *rr, const double *rz_new, hipStream_t s,
+                              double eps = -1.0, int64_t k = 0, int64_t *kdone = nullptr, double *rrfinal = nullptr,
+                              int64_t *hrec = nullptr);
+// D[(k * bs + i) * bs + j] = the sum in stored order of row k bs + i's entries in
+// column k bs + j, +0.0 where there is none (nblk * bs * bs doubles).
+hipError_t csr_diag_blocks_f64(int64_t n, int bs, const int64_t *row_ptr, const int32_t *col_idx,
+                               const double *values, double *D, hipStream_t s);
+
 // r = b - Ax; p = r (if p); *rr_out = r.r (if rr_out).  Ax == nullptr: Ax = 0
 // (r = b - 0.0).  clear2: two int64 the kernel zeroes (the convergence record).
 hipError_t residual_f64(int64_t n, const double *b, const double *Ax, double *r, double *p,
@@ -431,16 +458,17 @@ hipError_t preload_matvec_nrhs();
 hipError_t preload_spmv();
 hipError_t preload_spmm();
 hipError_t preload_pcg();
+hipError_t preload_pcg_block();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
-    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512
+    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512, PL_PCG_BLOCK = 1024
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
         {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg},
-        {PL_SPMM, preload_spmm}};
+        {PL_SPMM, preload_spmm}, {PL_PCG_BLOCK, preload_pcg_block}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

@@ -232,7 +232,7 @@ void free_shard(Shard &s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm) ncclCommDestroy(s.comm);
     for (char *p : {s.A, s.b, s.x, s.rh ? s.rh : s.r, s.p2, s.p3, s.Ap, s.pfull, s.p_alt, s.xfull, s.scal, s.sym_prow,
-                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.pc_minv})
+                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.pc_minv, s.pc_w, s.pc_z})
         if (p) (void)hipFree(p);
     if (s.ws.partials) (void)hipFree(s.ws.partials);
     if (s.ws.tickets) (void)hipFree(s.ws.tickets);

@@ -154,6 +154,53 @@
  *       r.r bit for bit on the same plan; so does minv == a power of two
  *       (alpha absorbs the factor, p carries it).
  *     - cgx_get_info: flags carries CGX_PRECOND_ACTIVE while a kind is set.
+ *   - Block-Jacobi preconditioning (cgx_set_precond_block,
+ *     cgx_set_precond_block_values; kind CGX_PC_BLOCK): M^-1 = W, the inverses
+ *     of A's bs x bs diagonal blocks, 2 <= bs <= CGX_MAX_PC_BLOCK, for systems
+ *     with bs coupled unknowns per node.  Block k covers rows [k bs,
+ *     min(n, (k+1) bs)); nblk = ceil(n / bs); when n % bs != 0 the last block
+ *     is t x t with t = n % bs (bs > n: one short block, M = A).  On the host
+ *     blocks are nblk * bs * bs doubles, block after block, row-major inside
+ *     one; a short block's unused rows and columns are +0.0 on output and
+ *     ignored on input.
+ *     - Extraction (cgx_csr_diag_blocks, on the device): D_k[i][j] is the sum,
+ *       from +0.0 in stored order, of row k bs + i's entries whose column is
+ *       k bs + j (a duplicate is two terms); +0.0 where there is none.
+ *     - Inversion (cgx_precond_block_invert, on the host, contraction off):
+ *       Cholesky D_k = L L^T from the lower triangle only (no symmetry check),
+ *       W_k = L^-T L^-1 with the lower triangle computed and mirrored.  A
+ *       pivot that is not finite or not > 0 is CGX_ERR_SHAPE naming the
+ *       lowest such block, its rows and the pivot.
+ *     - cgx_set_precond_block: extract, download, invert, upload (a one-time
+ *       cost).  When it fails the context keeps the preconditioner it had and
+ *       a later solve gives the bits it gave before; when it succeeds it ends
+ *       a solve in progress.  cgx_set_precond_block_values takes the caller's
+ *       W after cgx_precond_block_check (every used entry finite, every used
+ *       diagonal entry > 0; CGX_ERR_SHAPE names W[block][i][j], nothing
+ *       changes); whether those blocks are symmetric and positive definite is
+ *       the caller's business -- CG needs an SPD M.  cgx_set_csr turns the kind
+ *       off, as every kind.
+ *     - Order of z = W r (the contract): for row i of block k, with j over the
+ *       block's rows in ascending order, z_i = fl(W[i][0] r_0), then z_i =
+ *       fma(W[i][j], r_j, z_i) for j = 1, ...  So blocks whose off-diagonal
+ *       entries are 0 give CGX_PC_DIAG's z bit for bit.  z is stored (one more
+ *       n-vector on the context): the r update forms it from the new r it
+ *       holds, the x/p update reads it.  r.r and r.z are fixed-order sums in
+ *       an order of their own (not the diagonal kernels'): deterministic for a
+ *       given (n, bs).
+ *     - The iteration is otherwise the diagonal kinds': three launches in every
+ *       host form and x, the loop count and r.r the same bits across them for
+ *       a given plan; alpha = r.z_old / p.Ap, beta = r.z_new / r.z_old, the
+ *       stop on sqrt(r.r) < eps; stats and cgx_residual_norm unchanged.
+ *     - Refusals.  CGX_ERR_ARG: a context that is not a plain cgx_create_csr
+ *       context (a cgx_create_csr_nrhs context included), bs outside the range
+ *       (bs = 1 is CGX_PC_JACOBI), a NULL argument; cgx_set_precond(ctx,
+ *       CGX_PC_BLOCK) -- the kind has its own entry points, as CGX_PC_DIAG.
+ *       CGX_ERR_STATE: a call before the first cgx_set_csr;
+ *       cgx_get_precond_block while the kind is not CGX_PC_BLOCK;
+ *       cgx_get_precond_diag while it is.
+ *     - cgx_get_precond reports CGX_PC_BLOCK for both ways in; cgx_get_info
+ *       carries CGX_PRECOND_ACTIVE.
  *   - Several right-hand sides (cgx_create_csr_nrhs): nrhs (1..CGX_MAX_NRHS)
  *     systems A x_j = b_j on one CSR matrix, the CSR arrays read once per
  *     iteration (k_spmm_csr_f64).  The context is a cgx_create_csr context's
@@ -178,7 +225,8 @@
  *     - Refusals: at creation nrhs outside [1, CGX_MAX_NRHS], n < 1,
  *       n >= 2^31, nnz < 0 or any flag bit but CGX_TIMING (CGX_ERR_ARG, *ctx
  *       NULL, before the device is touched); cgx_generate_spd, a non-NULL A,
- *       cgx_residual_norm, cgx_set_precond and cgx_set_precond_diag
+ *       cgx_residual_norm, cgx_set_precond, cgx_set_precond_diag and
+ *       cgx_set_precond_block[_values]
  *       (CGX_ERR_ARG: batched CG has no preconditioned update kernels);
  *       cgx_solve_begin, cgx_solve and cgx_residual_norms before the first
  *       cgx_set_csr (CGX_ERR_STATE).
@@ -207,7 +255,9 @@ extern "C" {
                            cgx_create_csr and its entry points, and the reported bit
                            CGX_CSR_ACTIVE; likewise cgx_set_precond and its entry points,
                            and the reported bit CGX_PRECOND_ACTIVE; likewise
-                           cgx_create_csr_nrhs and cgx_spmm_csr (new functions only, no new bit) */
+                           cgx_create_csr_nrhs and cgx_spmm_csr (new functions only, no new bit);
+                           likewise cgx_set_precond_block and its entry points and the kind
+                           CGX_PC_BLOCK (new functions only, no new bit) */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -549,7 +599,36 @@ int cgx_precond_diag_check(int64_t n, const double *minv);
 int cgx_set_precond(cgx_ctx *ctx, int kind);            /* CGX_PC_NONE or CGX_PC_JACOBI */
 int cgx_set_precond_diag(cgx_ctx *ctx, const double *minv);   /* n host values; runs the check first */
 int cgx_get_precond(const cgx_ctx *ctx, int *kind);     /* CGX_PC_NONE on every other context */
-int cgx_get_precond_diag(cgx_ctx *ctx, double *minv);   /* the n values in use; CGX_ERR_STATE when none */
+int cgx_get_precond_diag(cgx_ctx *ctx, double *minv);   /* the n values in use; CGX_ERR_STATE when none or CGX_PC_BLOCK */
+
+/* ---- block-Jacobi preconditioning of a cgx_create_csr context (see "Sparse A" above) --------- */
+#define CGX_PC_BLOCK      3   /* M^-1 = the inverses of A's bs x bs diagonal blocks (reported by
+                                 cgx_get_precond; set by cgx_set_precond_block[_values]) */
+#define CGX_MAX_PC_BLOCK  8
+/* Blocks: nblk = ceil(n / bs) of bs * bs doubles, block after block, row-major inside a block;
+ * a short last block (n % bs rows) uses its leading entries, the rest is +0.0 on output and
+ * ignored on input. */
+/* Extracts the diagonal blocks on the device, inverts them on the host (cgx_precond_block_invert)
+ * and uploads the inverses: a one-time cost.  2 <= bs <= CGX_MAX_PC_BLOCK.  CGX_ERR_SHAPE names the
+ * lowest block that is not positive definite; the context then keeps the preconditioner it had. */
+int cgx_set_precond_block(cgx_ctx *ctx, int bs);
+/* The caller's inverse blocks (host); runs cgx_precond_block_check first and changes nothing when
+ * it fails.  Their symmetry and definiteness are the caller's business. */
+int cgx_set_precond_block_values(cgx_ctx *ctx, int bs, const double *W);
+/* The block size and (W != NULL) the inverse blocks in use; CGX_ERR_STATE unless the kind is CGX_PC_BLOCK. */
+int cgx_get_precond_block(cgx_ctx *ctx, int *bs, double *W);
+/* Host-only, no GPU needed.  W_k = (L L^T)^-1 with D_k = L L^T, reading D_k's lower triangle only;
+ * W_k is symmetric bit for bit.  CGX_ERR_SHAPE names the lowest block with a pivot that is not
+ * finite or not > 0, its rows and the pivot (W is then unspecified). */
+int cgx_precond_block_invert(int64_t n, int bs, const double *D, double *W);
+/* Host-only: CGX_OK, or CGX_ERR_SHAPE naming the first used entry W[block][i][j] that is not
+ * finite, or on the diagonal and not > 0 (CGX_ERR_ARG: n < 1, bs outside the range, W NULL). */
+int cgx_precond_block_check(int64_t n, int bs, const double *W);
+/* Kernel-level, device pointers as cgx_spmv_csr (row_ptr int64, col_idx int32, values double):
+ * D (nblk * bs * bs doubles, the layout above) = A's diagonal blocks, each entry the sum from
+ * +0.0 in stored order of the row's entries in that column.  The indices are not range-checked. */
+int cgx_csr_diag_blocks(int64_t n, int bs, const void *row_ptr, const void *col_idx, const void *values, void *D,
+                        void *stream);
 
 int cgx_destroy(cgx_ctx *ctx);
 int cgx_get_info(const cgx_ctx *ctx, cgx_info *info);
