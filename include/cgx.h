@@ -201,6 +201,14 @@
  *       cgx_get_precond_diag while it is.
  *     - cgx_get_precond reports CGX_PC_BLOCK for both ways in; cgx_get_info
  *       carries CGX_PRECOND_ACTIVE.
+ *     - Pinned by tests/test_gpu_pcg_probe.py (reference and bars in
+ *       tests/_pcg_probe.py) for every bs, every short last block t = 0 ..
+ *       bs - 1 with NaN in its unused slots, an unsymmetric W, and the
+ *       diagonal kinds at the edges of their pair loop: after each of three
+ *       fixed iterations from a rough x0 every element of x agrees with the
+ *       same recurrence in extended precision to 100 x the spread between
+ *       fp64 summation orders (at most 1.5e-11 of the terms added into that
+ *       element).
  *   - Several right-hand sides (cgx_create_csr_nrhs): nrhs (1..CGX_MAX_NRHS)
  *     systems A x_j = b_j on one CSR matrix, the CSR arrays read once per
  *     iteration (k_spmm_csr_f64).  The context is a cgx_create_csr context's

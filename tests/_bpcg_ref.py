@@ -17,9 +17,12 @@ point Jacobi needs two to five times block Jacobi's loops on these systems and p
 TABLE, measured with this file at eps = 1e-10: block-Jacobi loops, the ratio sqrt(r.r) / eps one iteration before
 the stop and at it, and point Jacobi's loops.  A loop count is asserted only where the reference alone stands a
 factor of 3 from the threshold on both sides (_pcg_ref.checked_reference's rule, `checked` below); every case of the
-table does.  Not to be used, they do not keep the factor: masked (1001, 2) and (1000, 2) at dec 2 (ratio at ~ 0.9),
-masked (2101, 8) at dec 4 (0.85 - 0.98), Poisson m = 7 and m = 12 at every bs tried, Poisson m = 5 at bs 3, 4, 8.
-The largest condition number of a diagonal block among the cases is 2.3e4."""
+table does.  The three large masked systems carry every block size 2 .. 8, so every instantiation of the block
+kernels solves a system of more than one thread block, with a short last block at n = 2101 and (but for bs = 7, which
+divides it) at n = 1001; tests/_pcg_probe.py has every short block at every bs.  The n = 5 systems carry bs in
+{2, 3, 4, 8}, the Poisson systems bs = 2.  Not to be used, they do not keep the factor: masked (1001, 2) and
+(1000, 2) at dec 2 (ratio at ~ 0.9), masked (2101, 8) at dec 4 (0.85 - 0.98), Poisson m = 7 and m = 12 at every bs
+tried, Poisson m = 5 at bs 3, 4, 8.  The largest condition number of a diagonal block among the cases is 2.3e4."""
 import functools
 
 import numpy as np
@@ -158,10 +161,13 @@ def jacobi_loops(A, b, max_iter=None):
 
 
 _rows("masked", 1001, 2, 4, {2: (7, 6.51, 0.040, 13), 3: (7, 6.40, 0.039, 18), 4: (7, 6.43, 0.040, 21),
+                             5: (7, 6.28, 0.037, 24), 6: (7, 6.59, 0.039, 29), 7: (7, 7.14, 0.038, 30),
                              8: (7, 6.73, 0.039, 35)})
 _rows("masked", 1000, 2, 4, {2: (7, 6.05, 0.036, 12), 3: (7, 6.00, 0.035, 17), 4: (7, 6.05, 0.035, 20),
+                             5: (7, 6.19, 0.034, 24), 6: (7, 6.23, 0.035, 29), 7: (7, 6.57, 0.032, 33),
                              8: (7, 6.80, 0.034, 35)})
 _rows("masked", 2101, 8, 2, {2: (6, 45.6, 0.122, 12), 3: (6, 45.5, 0.118, 16), 4: (6, 47.7, 0.120, 19),
+                             5: (6, 52.1, 0.133, 22), 6: (6, 52.5, 0.131, 26), 7: (6, 54.0, 0.129, 29),
                              8: (6, 54.9, 0.138, 34)})
 # n = 5: bs = 8 is n < bs, one short block, M = A, one loop
 _rows("masked", 5, 3, 2, {2: (5, 1.7e6, 1.1e-7, 5), 3: (5, 2.0e6, 1.4e-8, 5), 4: (3, 4.9e8, 5.7e-7, 5),
