@@ -185,9 +185,12 @@ def lib() -> ctypes.CDLL:
         "cgx_csr_check": ([i64, i64, vp, vp], i32),
         "cgx_create_csr": ([pctx, i64, i64, i32, i32], i32),
         "cgx_set_csr": ([vp, vp, vp, vp], i32),
+        "cgx_set_csr_f32": ([vp, vp, vp, vp], i32),
         "cgx_spmv_csr": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
+        "cgx_spmv_csr_f32": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_create_csr_nrhs": ([pctx, i64, i64, i32, i32, i32], i32),
         "cgx_spmm_csr": ([i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp], i32),
+        "cgx_spmm_csr_f32": ([i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp], i32),
         "cgx_precond_diag_check": ([i64, vp], i32),
         "cgx_set_precond": ([vp, i32], i32),
         "cgx_set_precond_diag": ([vp, vp], i32),
@@ -421,15 +424,22 @@ def matVec_nrhs(A: DeviceArray, V: DeviceArray, Out: DeviceArray, rows: int, col
            "cgx_matvec_nrhs")
 
 
-def _csr_arrays(indptr, indices=None, data=None):
+def _a_f32_flag(what: str, a_f32) -> bool:
+    _need(isinstance(a_f32, (bool, np.bool_)), f"{what}: a_f32 must be True or False (got {a_f32!r})")
+    return bool(a_f32)
+
+
+def _csr_arrays(indptr, indices=None, data=None, a_f32: bool = False):
     """(indptr int64, indices int32, data float64), contiguous; ``indptr`` may be
-    an object with ``.indptr / .indices / .data`` (no scipy needed)."""
+    an object with ``.indptr / .indices / .data`` (no scipy needed).  ``a_f32``:
+    data as float32 (a float64 array is rounded to nearest, as the dense
+    CGX_A_F32 path rounds A)."""
     if indices is None and data is None and hasattr(indptr, "indptr"):
         indptr, indices, data = indptr.indptr, indptr.indices, indptr.data
     _need(indices is not None and data is not None, "CSR: indptr, indices and data are needed")
     rp = np.ascontiguousarray(indptr, np.int64)
     ci = np.ascontiguousarray(indices, np.int32)
-    va = np.ascontiguousarray(data, np.float64)
+    va = np.ascontiguousarray(data, np.float32 if a_f32 else np.float64)
     _need(rp.ndim == 1 and ci.ndim == 1 and va.ndim == 1, "CSR: indptr, indices and data are one-dimensional")
     _need(ci.size == va.size, f"CSR: {ci.size} indices but {va.size} values")
     return rp, ci, va
@@ -447,12 +457,16 @@ def _csr_checked(what: str, rp, ci, rows: int, cols: int) -> None:
     _need(bad.size == 0, f"{what}: indices[{bad[0] if bad.size else 0}] outside [0, {cols})")
 
 
-def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int, cols: int) -> None:
+def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int, cols: int, *,
+             a_f32: bool = False) -> None:
     """out[i] = sum_e data[e] * v[indices[e]] over row i's entries, in stored
     order (k_spmv_csr_f64; the plan from CGX_SPMV_PLAN).  The structure comes
     as host arrays: it is checked (cgx_csr_check) and only then uploaded, so the
-    kernel never sees an index outside v."""
-    rp, ci, va = _csr_arrays(indptr, indices, data)
+    kernel never sees an index outside v.  ``a_f32=True`` (cgx_spmv_csr_f32): data
+    is cast to float32 and stays float32 on the device; the kernel widens it
+    exactly, so the result is this call's on ``data.astype(float32)`` bit for bit."""
+    a_f32 = _a_f32_flag("spmv_csr", a_f32)
+    rp, ci, va = _csr_arrays(indptr, indices, data, a_f32)
     _need(rows >= 1 and cols >= 1, "spmv_csr: need rows, cols >= 1")
     _need(rp.size == rows + 1, f"spmv_csr: indptr has {rp.size} entries, rows + 1 = {rows + 1} needed")
     _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_csr: float64 only")
@@ -462,7 +476,8 @@ def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int,
     _csr_checked("spmv_csr", rp, ci, rows, cols)
     d_rp, d_ci, d_va = DeviceArray.from_host(rp), DeviceArray.from_host(ci), DeviceArray.from_host(va)
     try:
-        _check(L.cgx_spmv_csr(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, v.ptr, out.ptr, None), "cgx_spmv_csr")
+        fn, name = (L.cgx_spmv_csr_f32, "cgx_spmv_csr_f32") if a_f32 else (L.cgx_spmv_csr, "cgx_spmv_csr")
+        _check(fn(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, v.ptr, out.ptr, None), name)
         _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
     finally:
         for d in (d_rp, d_ci, d_va):
@@ -470,12 +485,14 @@ def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int,
 
 
 def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int, cols: int, nrhs: int,
-             ldv: int | None = None, ldo: int | None = None) -> None:
+             ldv: int | None = None, ldo: int | None = None, *, a_f32: bool = False) -> None:
     """``nrhs`` sparse matVecs in one pass over the CSR arrays (k_spmm_csr_f64; the plan from
     CGX_SPMM_PLAN): Out[j*ldo + i] = sum_e data[e] * V[j*ldv + indices[e]].  Column j is
     :func:`spmv_csr`'s result on column j of V bit for bit at the same T.  The structure is
-    checked on the host before anything is uploaded, as :func:`spmv_csr` does."""
-    rp, ci, va = _csr_arrays(indptr, indices, data)
+    checked on the host before anything is uploaded, as :func:`spmv_csr` does.
+    ``a_f32=True`` (cgx_spmm_csr_f32): float32 data, as :func:`spmv_csr`'s."""
+    a_f32 = _a_f32_flag("spmm_csr", a_f32)
+    rp, ci, va = _csr_arrays(indptr, indices, data, a_f32)
     ldv, ldo = ldv or cols, ldo or rows
     _need(isinstance(nrhs, (int, np.integer)) and 1 <= nrhs <= CGX_MAX_NRHS,
           f"spmm_csr: nrhs must be in [1, {CGX_MAX_NRHS}] (got {nrhs})")
@@ -489,8 +506,8 @@ def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int,
     _csr_checked("spmm_csr", rp, ci, rows, cols)
     d_rp, d_ci, d_va = DeviceArray.from_host(rp), DeviceArray.from_host(ci), DeviceArray.from_host(va)
     try:
-        _check(L.cgx_spmm_csr(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, int(nrhs), V.ptr, ldv, Out.ptr, ldo, None),
-               "cgx_spmm_csr")
+        fn, name = (L.cgx_spmm_csr_f32, "cgx_spmm_csr_f32") if a_f32 else (L.cgx_spmm_csr, "cgx_spmm_csr")
+        _check(fn(rows, cols, d_rp.ptr, d_ci.ptr, d_va.ptr, int(nrhs), V.ptr, ldv, Out.ptr, ldo, None), name)
         _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
     finally:
         for d in (d_rp, d_ci, d_va):
@@ -676,16 +693,18 @@ class Solver:
 
     @classmethod
     def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64,
-                 precond=None, nrhs: int | None = None) -> "Solver":
+                 precond=None, nrhs: int | None = None, a_f32: bool = False) -> "Solver":
         """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)
         and, with ``precond`` ("jacobi", an array or ``("block", bs)``), its preconditioner (:meth:`set_precond`).
-        ``nrhs=K``: K systems on the matrix solved together (:meth:`csr`; no preconditioner)."""
-        rp, ci, va = _csr_arrays(indptr, indices, data)
+        ``nrhs=K``: K systems on the matrix solved together (:meth:`csr`; no preconditioner).
+        ``a_f32=True``: float-stored values (:meth:`set_csr`)."""
+        a_f32 = _a_f32_flag("from_csr", a_f32)
+        rp, ci, va = _csr_arrays(indptr, indices, data, a_f32)
         _need(rp.size >= 2, "from_csr: indptr needs n + 1 >= 2 entries")
         _need(nrhs is None or precond is None, "from_csr: no preconditioner with several right-hand sides")
         s = cls.csr(rp.size - 1, int(ci.size), nrhs=nrhs, device=device, flags=flags)
         try:
-            s.set_csr(rp, ci, va)
+            s.set_csr(rp, ci, va, a_f32=a_f32)
             if precond is not None:
                 s.set_precond(precond)
         except Exception:
@@ -693,15 +712,24 @@ class Solver:
             raise
         return s
 
-    def set_csr(self, indptr, indices=None, data=None) -> None:
+    def set_csr(self, indptr, indices=None, data=None, *, a_f32: bool = False) -> None:
         """cgx_set_csr: the matrix of a ``csr_nnz`` solver from host arrays (cast
         to int64 / int32 / float64).  The structure is checked before anything is
-        uploaded: CgxError(-4) names the first offence and the earlier matrix stays."""
+        uploaded: CgxError(-4) names the first offence and the earlier matrix stays.
+        ``a_f32=True`` (cgx_set_csr_f32): data is cast to float32 (float64 rounds to
+        nearest) and stays float32 on the device, 8 bytes per entry streamed in
+        place of 12; all arithmetic is fp64 on the exactly widened values, so the
+        solver gives the bits it gives for ``data.astype(float32).astype(float64)``.
+        ``info().flags`` carries CGX_A_F32 until the next ``set_csr`` without it."""
+        a_f32 = _a_f32_flag("set_csr", a_f32)
         _need(getattr(self, "csr_nnz", None) is not None, "set_csr: the solver was not created with csr_nnz=")
-        rp, ci, va = _csr_arrays(indptr, indices, data)
+        rp, ci, va = _csr_arrays(indptr, indices, data, a_f32)
         _need(rp.size == self.n + 1, f"set_csr: indptr has {rp.size} entries, n + 1 = {self.n + 1} needed")
         _need(ci.size <= self.csr_nnz, f"set_csr: {ci.size} entries, the solver has room for {self.csr_nnz}")
-        _check(lib().cgx_set_csr(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr")
+        if a_f32:
+            _check(lib().cgx_set_csr_f32(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr_f32")
+        else:
+            _check(lib().cgx_set_csr(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr")
 
     def set_precond(self, precond) -> None:
         """Diagonal preconditioning of a ``csr_nnz`` solver: ``"jacobi"`` (1 / diag(A),

@@ -43,7 +43,12 @@
  * solve is preconditioned with 1 / diag(A); --stats adds "precond: jacobi")
  * or --block-jacobi BS (cgx_set_precond_block: preconditioned with the
  * inverses of A's BS x BS diagonal blocks, 2 <= BS <= 8; --stats adds
- * "precond: block-jacobi BS").
+ * "precond: block-jacobi BS"),
+ * --csr-a32 (--csr with the file's values parsed and kept as float, what the
+ * reference's fscanf("%f") holds, on the host and on the GPU: cgx_set_csr_f32,
+ * 8 bytes per entry streamed in place of 12, all arithmetic still fp64 on the
+ * exactly widened values; takes --jacobi or --block-jacobi BS as --csr does and
+ * is given without --csr; --stats adds "values: float").
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -127,8 +132,10 @@ static void usage(const char *prog) {
             "       %s --nrhs K ... (one GPU, fp64: K systems on one matrix; vectorb and initialguess hold K*N values)\n"
             "       %s --csr [--jacobi | --block-jacobi BS] ... (one GPU, fp64: the matrix's non-zero entries only, solved\n"
             "          as a sparse CSR system; --jacobi: preconditioned with 1 / diag(A); --block-jacobi BS: with the\n"
-            "          inverses of A's BS x BS diagonal blocks, BS in 2..8)\n",
-            prog, prog, prog, prog);
+            "          inverses of A's BS x BS diagonal blocks, BS in 2..8)\n"
+            "       %s --csr-a32 [--jacobi | --block-jacobi BS] ... (--csr with the values parsed and kept as float, fp64\n"
+            "          arithmetic; given without --csr)\n",
+            prog, prog, prog, prog, prog);
 }
 
 static int die_cgx(int rc, const char *what) {
@@ -272,38 +279,50 @@ static int stream_parse(a_stream *st) {
 typedef struct {
     int64_t *row_ptr;
     int32_t *col_idx;
-    double *values;
+    void *values; /* double, or float with --csr-a32 (as_float): parsed, kept and uploaded as such */
     int64_t nnz, cap;
 } csr_host;
 
-static int csr_parse(cgx_text *text, int64_t n, int64_t block_rows, double *blk, int threads, csr_host *m) {
+static int csr_parse(cgx_text *text, int64_t n, int64_t block_rows, void *blk, int threads, csr_host *m,
+                     int as_float) {
+    const size_t ves = as_float ? sizeof(float) : sizeof(double);
     m->row_ptr = malloc((size_t)(n + 1) * sizeof(int64_t));
     m->cap = 8 * n > 1024 ? 8 * n : 1024;
     m->col_idx = malloc((size_t)m->cap * sizeof(int32_t));
-    m->values = malloc((size_t)m->cap * sizeof(double));
+    m->values = malloc((size_t)m->cap * ves);
     m->nnz = 0;
     if (!m->row_ptr || !m->col_idx || !m->values) return -9;
     m->row_ptr[0] = 0;
     for (int64_t row0 = 0; row0 < n; row0 += block_rows) {
         const int64_t rows = row0 + block_rows <= n ? block_rows : n - row0;
-        const int rc = cgx_text_read_range(text, row0 * n, rows * n, 0, blk, threads);
+        const int rc = cgx_text_read_range(text, row0 * n, rows * n, as_float, blk, threads);
         if (rc != 0) return rc;
         for (int64_t i = 0; i < rows; ++i) {
-            const double *row = blk + (size_t)i * (size_t)n;
             if (m->nnz + n > m->cap) { /* room for a full row */
                 const int64_t cap = 2 * m->cap > m->nnz + n ? 2 * m->cap : m->nnz + n;
                 int32_t *ci = realloc(m->col_idx, (size_t)cap * sizeof(int32_t));
                 if (ci) m->col_idx = ci;
-                double *va = realloc(m->values, (size_t)cap * sizeof(double));
+                void *va = realloc(m->values, (size_t)cap * ves);
                 if (va) m->values = va;
                 if (!ci || !va) return -9;
                 m->cap = cap;
             }
-            for (int64_t j = 0; j < n; ++j)
-                if (row[j] != 0.0) { /* +0 and -0 are dropped; everything else is an entry */
-                    m->col_idx[m->nnz] = (int32_t)j;
-                    m->values[m->nnz++] = row[j];
-                }
+            /* +0 and -0 are dropped; everything else is an entry */
+            if (as_float) {
+                const float *row = (const float *)blk + (size_t)i * (size_t)n;
+                for (int64_t j = 0; j < n; ++j)
+                    if (row[j] != 0.0f) {
+                        m->col_idx[m->nnz] = (int32_t)j;
+                        ((float *)m->values)[m->nnz++] = row[j];
+                    }
+            } else {
+                const double *row = (const double *)blk + (size_t)i * (size_t)n;
+                for (int64_t j = 0; j < n; ++j)
+                    if (row[j] != 0.0) {
+                        m->col_idx[m->nnz] = (int32_t)j;
+                        ((double *)m->values)[m->nnz++] = row[j];
+                    }
+            }
             m->row_ptr[row0 + i + 1] = m->nnz;
         }
     }
@@ -332,6 +351,7 @@ static int opt_double(const char *name, const char *v, double *out) {
 int main(int argc, char **argv) {
     const double t_prog0 = now_s();
     int gpus = 1, fp32ref = 0, symmetric = 0, print_x = 0, stats = 0, p2p = 0, a_fp32 = 0, csr = 0, jacobi = 0;
+    int csr_a32 = 0; /* --csr-a32: becomes csr = 1 once the combinations are checked */
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
@@ -353,6 +373,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "--a-fp32")) a_fp32 = 1;
         else if (!strcmp(a, "--p2p")) p2p = 1;
         else if (!strcmp(a, "--csr")) csr = 1;
+        else if (!strcmp(a, "--csr-a32")) csr_a32 = 1;
         else if (!strcmp(a, "--jacobi")) jacobi = 1;
         else if (!strcmp(a, "--block-jacobi")) {
             if (has_val && !opt_ll(a, argv[++i], &block_bs)) return 2;
@@ -392,6 +413,11 @@ int main(int argc, char **argv) {
     }
     if (gpus < 1) { fprintf(stderr, "--gpus must be >= 1\n"); return 2; }
     if (gpus > 32) { fprintf(stderr, "--gpus must be <= 32\n"); return 2; }
+    if (csr_a32 && (csr || fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
+        fprintf(stderr, "--csr-a32 is --csr with float-stored values: it is given alone (no --csr, --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
+        return 2;
+    }
+    if (csr_a32) csr = 1;
     if (p2p && symmetric) {
         fprintf(stderr, "--p2p is an exchange of several row blocks (--symmetric is one GPU)\n");
         return 2;
@@ -527,7 +553,7 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "can't allocate memory for vector\n");
                 return 1;
             }
-            const int prc = csr_parse(text, n, block_rows, (double *)Abuf.p, threads, &csrm);
+            const int prc = csr_parse(text, n, block_rows, Abuf.p, threads, &csrm, csr_a32);
             if (prc == -9) fprintf(stderr, "can't allocate memory for vector\n");
             else if (prc) fprintf(stderr, prc == -2 ? "%s: fewer than %lld numbers\n" : "%s: malformed number\n", pos[0],
                                   (long long)(n * n));
@@ -639,8 +665,9 @@ int main(int argc, char **argv) {
         t_dist1 = now_s();
         if (rc != CGX_OK) return die_cgx(rc, "cgx_generate_spd");
     } else if (csr) {
-        rc = cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, csrm.values);
-        if (rc != CGX_OK) return die_cgx(rc, "cgx_set_csr");
+        rc = csr_a32 ? cgx_set_csr_f32(ctx, csrm.row_ptr, csrm.col_idx, (const float *)csrm.values)
+                     : cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, (const double *)csrm.values);
+        if (rc != CGX_OK) return die_cgx(rc, csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
         if (jacobi) { /* 1 / diag(A) from the uploaded matrix; a diagonal it refuses ends the run */
             rc = cgx_set_precond(ctx, CGX_PC_JACOBI);
             if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond");
@@ -702,6 +729,7 @@ int main(int argc, char **argv) {
         printf("iterations: %lld converged: %d residual_norm: %.6e\n", (long long)st.iterations, st.converged,
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
     if (stats && csr) printf("nnz: %lld\n", (long long)csrm.nnz);
+    if (stats && csr_a32) printf("values: float\n");
     if (stats && jacobi) printf("precond: jacobi\n");
     if (stats && block_bs > 0) printf("precond: block-jacobi %lld\n", block_bs);
     if (stats && nrhs > 0)

@@ -7,6 +7,11 @@
 // host (cgx_csr_check) before anything is uploaded: no path of a context
 // reaches the kernel with indices that did not pass.
 //
+// cgx_set_csr_f32 uploads float values, which stay float on the device in the
+// same value buffer (cgx_ctx::csr_f32); every launch that reads the values
+// takes them as csr_values(c), and the kernels widen them exactly, so the
+// context gives the bits a double-valued one gives on (double)values[e].
+//
 // cgx_set_precond / cgx_set_precond_diag put n positive values minv on the
 // device (1 / diag(A) extracted there, or the caller's); while they are set,
 // do_begin and the two update launches run the PCG kernels (cgx_pcg.hip).
@@ -31,7 +36,8 @@ int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
                                  "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
     Shard &s = c->sh[0];
     TRY(set_dev(s));
-    s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu);
+    s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu,
+                           c->csr_f32);
     c->csr_plan_user = true;
     return CGX_OK;
 }
@@ -98,7 +104,7 @@ static int pc_jacobi(cgx_ctx *c) {
         pin[0] = ~0ull;
         HIPT(hipMemcpyAsync(slot(s, S_PCBAD), pin, 8, hipMemcpyHostToDevice, s.stream));
         HIPT(csr_diag_minv_f64(c->n, reinterpret_cast<const int64_t *>(s.csr_rp),
-                               reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(fresh),
+                               reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(fresh),
                                static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
         HIPT(hipMemcpyAsync(pin, slot(s, S_PCBAD), 8, hipMemcpyDeviceToHost, s.stream));
         HIPT(hipStreamSynchronize(s.stream));
@@ -171,6 +177,78 @@ static int pc_block_install(cgx_ctx *c, int bs, const double *W) {
     return CGX_OK;
 }
 
+// cgx_set_csr (f32 = false: values is double[nnz]) and cgx_set_csr_f32 (float[nnz]):
+// the same checks in the same order, then the upload.  Float values take the
+// first 4 nnz bytes of the value buffer and stay float there; the context's
+// value type changes only once everything is on the device.
+static int csr_upload(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, const void *values, bool f32,
+                      const char *what) {
+    if (!c) return fail(CGX_ERR_ARG, "%s: ctx is NULL", what);
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "%s: not a cgx_create_csr context", what);
+    if (!row_ptr) return fail(CGX_ERR_ARG, "%s: row_ptr is NULL", what);
+    const int64_t nnz = row_ptr[c->n];  // the entry count a valid row_ptr states; the check below tests the rest
+    if (nnz < 0) return fail(CGX_ERR_SHAPE, "%s: row_ptr[n] = %lld is negative", what, (long long)nnz);
+    if (nnz > c->csr_cap)
+        return fail(CGX_ERR_SHAPE, "%s: %lld entries, the context has room for %lld", what, (long long)nnz,
+                    (long long)c->csr_cap);
+    if (nnz > 0 && (!col_idx || !values)) return fail(CGX_ERR_ARG, "%s: col_idx / values is NULL", what);
+    TRY(cgx_csr_check(c->n, nnz, row_ptr, col_idx));  // nothing is uploaded when it fails
+    Shard &s = c->sh[0];
+    TRY(sync_all(c));  // iterations still enqueued read the arrays
+    TRY(set_dev(s));
+    HIPT(hipMemcpyAsync(s.csr_rp, row_ptr, (size_t)(c->n + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    if (nnz > 0) {
+        HIPT(hipMemcpyAsync(s.csr_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, s.stream));
+        HIPT(hipMemcpyAsync(s.csr_val, values, (size_t)nnz * (f32 ? 4 : 8), hipMemcpyHostToDevice, s.stream));
+    }
+    HIPT(hipStreamSynchronize(s.stream));
+    c->csr_nnz = nnz;
+    c->csr_f32 = f32;
+    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
+    if (!c->csr_plan_user) {
+        if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs), 0, -1, 0, f32);
+        else s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 0, -1, 0, f32);
+    }
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
+// cgx_spmv_csr / cgx_spmv_csr_f32
+static int spmv_csr_any(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, CsrValues values,
+                        const void *v, void *out, void *stream, const char *what) {
+    if (rows < 0 || cols < 0) return fail(CGX_ERR_SHAPE, "%s: bad shape", what);
+    if (!row_ptr || !col_idx || !values.p || !v || !out) return fail(CGX_ERR_ARG, "%s: NULL pointer", what);
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    RedWs ws;
+    TRY(dev_ws(&ws));
+    // the entry count lives on the device: T comes from CGX_SPMV_PLAN or, without it, is 8
+    const MatvecPlan pl = plan_spmv_csr(dev, rows, /*nnz=*/-1, 0, -1, 0, values.f32);
+    HIPT(spmv_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx), values, rows,
+                      static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
+                      static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
+// cgx_spmm_csr / cgx_spmm_csr_f32
+static int spmm_csr_any(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, CsrValues values,
+                        int nrhs, const void *V, int64_t ldv, void *Out, int64_t ldo, void *stream, const char *what) {
+    if (nrhs < 1 || nrhs > CGX_MAX_NRHS)
+        return fail(CGX_ERR_ARG, "%s: nrhs must be in [1, %d] (got %d)", what, CGX_MAX_NRHS, nrhs);
+    if (!row_ptr || !col_idx || !values.p || !V || !Out) return fail(CGX_ERR_ARG, "%s: NULL pointer", what);
+    if (rows < 0 || cols < 0 || (nrhs > 1 && (ldv < cols || ldo < rows)))
+        return fail(CGX_ERR_SHAPE, "%s: bad shape", what);
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    const RedWs none{nullptr, nullptr};  // no fused dot: no reduction scratch
+    // the entry count lives on the device: T comes from CGX_SPMM_PLAN or, without it, is 8
+    const MatvecPlan pl = plan_spmm_csr(dev, rows, /*nnz=*/-1, nrhs_width(nrhs), 0, -1, 0, values.f32);
+    HIPT(spmm_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx), values, rows,
+                      nrhs, static_cast<const double *>(V), ldv, static_cast<double *>(Out), ldo, nullptr, 0, nullptr,
+                      none, static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
 }  // namespace cgxh
 
 extern "C" {
@@ -237,7 +315,7 @@ int cgx_set_precond_block(cgx_ctx *c, int bs) {
     TRY(pc_alloc(s, (int64_t)cnt, &dD));
     auto extract = [&]() -> int {
         HIPT(csr_diag_blocks_f64(c->n, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
-                                 reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(dD), s.stream));
+                                 reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(dD), s.stream));
         HIPT(hipMemcpyAsync(D.data(), dD, cnt * 8, hipMemcpyDeviceToHost, s.stream));
         HIPT(hipStreamSynchronize(s.stream));
         return CGX_OK;
@@ -327,49 +405,22 @@ int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t 
 
 int cgx_set_csr(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, const double *values) {
     const Range range_("cgx_set_csr");
-    if (!c) return fail(CGX_ERR_ARG, "cgx_set_csr: ctx is NULL");
-    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_csr: not a cgx_create_csr context");
-    if (!row_ptr) return fail(CGX_ERR_ARG, "cgx_set_csr: row_ptr is NULL");
-    const int64_t nnz = row_ptr[c->n];  // the entry count a valid row_ptr states; the check below tests the rest
-    if (nnz < 0) return fail(CGX_ERR_SHAPE, "cgx_set_csr: row_ptr[n] = %lld is negative", (long long)nnz);
-    if (nnz > c->csr_cap)
-        return fail(CGX_ERR_SHAPE, "cgx_set_csr: %lld entries, the context has room for %lld", (long long)nnz,
-                    (long long)c->csr_cap);
-    if (nnz > 0 && (!col_idx || !values)) return fail(CGX_ERR_ARG, "cgx_set_csr: col_idx / values is NULL");
-    TRY(cgx_csr_check(c->n, nnz, row_ptr, col_idx));  // nothing is uploaded when it fails
-    Shard &s = c->sh[0];
-    TRY(sync_all(c));  // iterations still enqueued read the arrays
-    TRY(set_dev(s));
-    HIPT(hipMemcpyAsync(s.csr_rp, row_ptr, (size_t)(c->n + 1) * 8, hipMemcpyHostToDevice, s.stream));
-    if (nnz > 0) {
-        HIPT(hipMemcpyAsync(s.csr_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, s.stream));
-        HIPT(hipMemcpyAsync(s.csr_val, values, (size_t)nnz * 8, hipMemcpyHostToDevice, s.stream));
-    }
-    HIPT(hipStreamSynchronize(s.stream));
-    c->csr_nnz = nnz;
-    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
-    if (!c->csr_plan_user) {
-        if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs));
-        else s.plan = plan_spmv_csr(s.dev, s.nloc, nnz);
-    }
-    c->state = ST_IDLE;
-    return CGX_OK;
+    return csr_upload(c, row_ptr, col_idx, values, /*f32=*/false, "cgx_set_csr");
+}
+
+int cgx_set_csr_f32(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, const float *values) {
+    const Range range_("cgx_set_csr_f32");
+    return csr_upload(c, row_ptr, col_idx, values, /*f32=*/true, "cgx_set_csr_f32");
 }
 
 int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const void *values,
                  const void *v, void *out, void *stream) {
-    if (rows < 0 || cols < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_csr: bad shape");
-    if (!row_ptr || !col_idx || !values || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_csr: NULL pointer");
-    int dev = 0;
-    HIPT(hipGetDevice(&dev));
-    RedWs ws;
-    TRY(dev_ws(&ws));
-    // the entry count lives on the device: T comes from CGX_SPMV_PLAN or, without it, is 8
-    const MatvecPlan pl = plan_spmv_csr(dev, rows, /*nnz=*/-1);
-    HIPT(spmv_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
-                      static_cast<const double *>(values), rows, static_cast<const double *>(v),
-                      static_cast<double *>(out), nullptr, nullptr, ws, static_cast<hipStream_t>(stream)));
-    return CGX_OK;
+    return spmv_csr_any(rows, cols, row_ptr, col_idx, CsrValues(values, false), v, out, stream, "cgx_spmv_csr");
+}
+
+int cgx_spmv_csr_f32(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const float *values,
+                     const void *v, void *out, void *stream) {
+    return spmv_csr_any(rows, cols, row_ptr, col_idx, CsrValues(values), v, out, stream, "cgx_spmv_csr_f32");
 }
 
 int cgx_csr_diag_blocks(int64_t n, int bs, const void *row_ptr, const void *col_idx, const void *values, void *D,
@@ -386,20 +437,14 @@ int cgx_csr_diag_blocks(int64_t n, int bs, const void *row_ptr, const void *col_
 
 int cgx_spmm_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const void *values, int nrhs,
                  const void *V, int64_t ldv, void *Out, int64_t ldo, void *stream) {
-    if (nrhs < 1 || nrhs > CGX_MAX_NRHS)
-        return fail(CGX_ERR_ARG, "cgx_spmm_csr: nrhs must be in [1, %d] (got %d)", CGX_MAX_NRHS, nrhs);
-    if (!row_ptr || !col_idx || !values || !V || !Out) return fail(CGX_ERR_ARG, "cgx_spmm_csr: NULL pointer");
-    if (rows < 0 || cols < 0 || (nrhs > 1 && (ldv < cols || ldo < rows)))
-        return fail(CGX_ERR_SHAPE, "cgx_spmm_csr: bad shape");
-    int dev = 0;
-    HIPT(hipGetDevice(&dev));
-    const RedWs none{nullptr, nullptr};  // no fused dot: no reduction scratch
-    // the entry count lives on the device: T comes from CGX_SPMM_PLAN or, without it, is 8
-    const MatvecPlan pl = plan_spmm_csr(dev, rows, /*nnz=*/-1, nrhs_width(nrhs));
-    HIPT(spmm_csr_f64(pl, static_cast<const int64_t *>(row_ptr), static_cast<const int32_t *>(col_idx),
-                      static_cast<const double *>(values), rows, nrhs, static_cast<const double *>(V), ldv,
-                      static_cast<double *>(Out), ldo, nullptr, 0, nullptr, none, static_cast<hipStream_t>(stream)));
-    return CGX_OK;
+    return spmm_csr_any(rows, cols, row_ptr, col_idx, CsrValues(values, false), nrhs, V, ldv, Out, ldo, stream,
+                        "cgx_spmm_csr");
+}
+
+int cgx_spmm_csr_f32(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const float *values,
+                     int nrhs, const void *V, int64_t ldv, void *Out, int64_t ldo, void *stream) {
+    return spmm_csr_any(rows, cols, row_ptr, col_idx, CsrValues(values), nrhs, V, ldv, Out, ldo, stream,
+                        "cgx_spmm_csr_f32");
 }
 
 }  // extern "C"

@@ -187,7 +187,8 @@ struct Shard {
     char *A = nullptr, *b = nullptr, *x = nullptr, *r = nullptr, *Ap = nullptr, *pfull = nullptr,
          *xfull = nullptr, *scal = nullptr;
     char *pown = nullptr;  // this shard's p: pfull + row0 (dense, CSR) or the slab interior (Poisson)
-    // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap]); no s.A
+    // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap], or the
+    // first half of it as float[csr_cap] while cgx_ctx::csr_f32); no s.A
     char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
     char *pc_minv = nullptr;  // ... and the preconditioner's n values (cgx_ctx::pc_kind JACOBI or DIAG)
     // CGX_PC_BLOCK: the inverse blocks, entry (i, j) of block k at pc_w[(i * bs + j) * pc_wld + k], and z = W r
@@ -291,8 +292,11 @@ struct cgx_ctx {
     // cgx_create_csr: room for csr_cap entries; csr_nnz = the entries of the
     // matrix cgx_set_csr uploaded (-1: none yet, nothing may multiply);
     // csr_plan_user: cgx_set_matvec_plan chose the plan (cgx_set_csr keeps it)
+    // csr_f32: cgx_set_csr_f32 uploaded the values, floats in sh[0].csr_val
+    // (csr_values(c) is what every launch reads them through)
     int64_t csr_cap = 0, csr_nnz = -1;
     bool csr_plan_user = false;
+    bool csr_f32 = false;
     // cgx_set_precond / cgx_set_precond_diag: CGX_PC_NONE, or the iteration runs the PCG kernels on
     // sh[0].pc_minv (cgx_pcg.hip); cgx_set_csr goes back to CGX_PC_NONE
     int pc_kind = CGX_PC_NONE;
@@ -400,6 +404,8 @@ namespace cgxh {
 
 inline bool f32ref(const cgx_ctx *c) { return (c->flags & CGX_F32_REF) != 0; }
 inline bool a32(const cgx_ctx *c) { return (c->flags & CGX_A_F32) != 0; }
+// a cgx_create_csr context's values with their type (double, or float after cgx_set_csr_f32)
+inline CsrValues csr_values(const cgx_ctx *c) { return CsrValues(c->sh[0].csr_val, c->csr_f32); }
 inline void *slot(const Shard &s, int i) { return s.scal + 8 * i; }
 inline bool p2p(const cgx_ctx *c) { return (c->flags & CGX_COMM_P2P) != 0; }
 // Where a kernel writes its (partial) scalar: the global slot directly when

@@ -200,11 +200,24 @@ hipError_t nrhs_update_xp_f64(int64_t n, int64_t ld, int nrhs, int64_t k, double
 // for a fixed grid).  The indices are not range-checked here (cgx_csr_check).
 // The instantiated (T, policy): T in {2, 4, 8, 16, 32, 64}, policy 2 or 8.
 bool spmv_csr_plan_ok(int T, int nt);
+// The values of a CSR matrix: double[nnz], or float[nnz] (cgx_set_csr_f32),
+// which every kernel below widens exactly with (double) before the same fp64
+// operations in the same order: a float-valued launch gives the bits of a
+// double-valued one on (double)values[e].  A pointer converts by its type.
+struct CsrValues {
+    const void *p;
+    bool f32;
+    CsrValues(const double *d) : p(d), f32(false) {}
+    CsrValues(const float *f) : p(f), f32(true) {}
+    CsrValues(const void *q, bool is_f32) : p(q), f32(is_f32) {}
+};
 // T <= 0 / nt < 0 / blocks_per_cu <= 0 pick the defaults (T from the mean row
 // length nnz / rows, 8 when nnz < 0; env CGX_SPMV_PLAN="T=..,nt=..,bpc=.." may override with an
-// instantiated plan).
-MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T = 0, int nt = -1, int blocks_per_cu = 0);
-hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+// instantiated plan).  f32: the grid comes from the float-valued kernel's
+// occupancy; the default T is the same for both value types.
+MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T = 0, int nt = -1, int blocks_per_cu = 0,
+                         bool f32 = false);
+hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                         int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
                         const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
 
@@ -220,9 +233,11 @@ hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int3
 bool spmm_csr_plan_ok(int K, int T, int nt);
 // T <= 0 / nt < 0 / blocks_per_cu <= 0 pick the defaults (T from the mean row
 // length nnz / rows, 8 when nnz < 0; env CGX_SPMM_PLAN="T=..,nt=..,bpc=.."
-// may override with an instantiated plan).  pl.nrhs = K, pl.csr = 1.
-MatvecPlan plan_spmm_csr(int device, int64_t rows, int64_t nnz, int K, int T = 0, int nt = -1, int blocks_per_cu = 0);
-hipError_t spmm_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+// may override with an instantiated plan).  pl.nrhs = K, pl.csr = 1.  f32 as
+// plan_spmv_csr's.
+MatvecPlan plan_spmm_csr(int device, int64_t rows, int64_t nnz, int K, int T = 0, int nt = -1, int blocks_per_cu = 0,
+                         bool f32 = false);
+hipError_t spmm_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                         int64_t rows, int nrhs, const double *V, int64_t ldv, double *Out, int64_t ldo,
                         const double *pown, int64_t ldp, double *dot_out, const RedWs &ws, hipStream_t s,
                         const int64_t *gate = nullptr, int64_t *ts = nullptr);
@@ -248,7 +263,7 @@ hipError_t pcg_update_xp_f64(int64_t n, double *x, double *p, const double *r, c
 // minv[i] = 1.0 / d_i, d_i = the sum in stored order of row i's entries in
 // column i.  A row without one, or with d_i not finite or not > 0, stores d_i
 // instead (-0.0: no entry) and lowers *bad (preset to all ones) to its index.
-hipError_t csr_diag_minv_f64(int64_t n, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+hipError_t csr_diag_minv_f64(int64_t n, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                              double *minv, unsigned long long *bad, hipStream_t s);
 
 // ---- block-Jacobi preconditioned CG on CSR contexts (cgx_pcg_block.hip) --------------
@@ -276,7 +291,7 @@ hipError_t pcgb_update_xp_f64(int64_t n, double *x, double *p, const double *z, 
 // D[(k * bs + i) * bs + j] = the sum in stored order of row k bs + i's entries in
 // column k bs + j, +0.0 where there is none (nblk * bs * bs doubles).
 hipError_t csr_diag_blocks_f64(int64_t n, int bs, const int64_t *row_ptr, const int32_t *col_idx,
-                               const double *values, double *D, hipStream_t s);
+                               CsrValues values, double *D, hipStream_t s);
 
 // r = b - Ax; p = r (if p); *rr_out = r.r (if rr_out).  Ax == nullptr: Ax = 0
 // (r = b - 0.0).  clear2: two int64 the kernel zeroes (the convergence record).

@@ -168,7 +168,7 @@ static int nrhs_matvec(cgx_ctx *c, const char *vec, bool with_dot, int64_t k, bo
     const int64_t *gate = gated ? &nr->sc->alldone : nullptr;
     if (c->op == OP_CSR) {  // the indices were checked on the host before they were uploaded (cgx_set_csr)
         HIPT(spmm_csr_f64(nr->plan, reinterpret_cast<const int64_t *>(s.csr_rp),
-                          reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), s.nloc, nr->nrhs, f64(vec), c->lda,
+                          reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), s.nloc, nr->nrhs, f64(vec), c->lda,
                           f64(nr->Ap), c->lda, pown, c->lda, dots, nr->ws, s.stream, gate));
     } else {
         HIPT(matvec_nrhs_f64(nr->plan, f64(s.A), c->lda, s.nloc, c->lda, nr->nrhs, f64(vec), c->lda, f64(nr->Ap), c->lda,
@@ -324,7 +324,7 @@ int nrhs_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
                                      "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
         TRY(set_dev(c->sh[0]));
         nr->plan = plan_spmm_csr(c->sh[0].dev, c->sh[0].nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, K, 64 / R, nt,
-                                 blocks_per_cu);
+                                 blocks_per_cu, c->csr_f32);
         c->csr_plan_user = true;
         return CGX_OK;
     }

@@ -187,9 +187,12 @@ __global__ __launch_bounds__(kNT) void k_pcg_update_xp_f64(int64_t n, double *__
 // a sum started from +0.0 is never -0.0) and takes part in the atomicMin that
 // leaves the lowest such row in *bad (the host set it to all ones).  The
 // indices passed cgx_csr_check (cgx_set_csr), so every e is inside the arrays.
+// VT = float (a float-valued context): each entry is widened exactly and d is
+// the same double sum.
+template <class VT>
 __global__ __launch_bounds__(kNT) void k_csr_diag_minv(int64_t n, const int64_t *__restrict__ row_ptr,
                                                        const int32_t *__restrict__ col_idx,
-                                                       const double *__restrict__ values, double *__restrict__ minv,
+                                                       const VT *__restrict__ values, double *__restrict__ minv,
                                                        unsigned long long *bad) {
 #pragma clang fp contract(off)
     for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(kNT) void k_csr_diag_minv(int64_t n, const int64_t 
         const int64_t e1 = row_ptr[i + 1];
         for (int64_t e = row_ptr[i]; e < e1; ++e)
             if ((int64_t)col_idx[e] == i) {
-                d = d + values[e];
+                d = d + (double)values[e];
                 found = true;
             }
         const bool good = found && d > 0.0 && d < __builtin_inf();
@@ -241,17 +244,21 @@ hipError_t pcg_update_xp_f64(int64_t n, double *x, double *p, const double *r, c
     return hipGetLastError();
 }
 
-hipError_t csr_diag_minv_f64(int64_t n, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+hipError_t csr_diag_minv_f64(int64_t n, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                              double *minv, unsigned long long *bad, hipStream_t s) {
-    hipLaunchKernelGGL(k_csr_diag_minv, dim3(grid_1d(n, kNT, 65536)), dim3(kNT), 0, s, n, row_ptr, col_idx, values,
-                       minv, bad);
+    if (values.f32)
+        hipLaunchKernelGGL(k_csr_diag_minv<float>, dim3(grid_1d(n, kNT, 65536)), dim3(kNT), 0, s, n, row_ptr, col_idx,
+                           static_cast<const float *>(values.p), minv, bad);
+    else
+        hipLaunchKernelGGL(k_csr_diag_minv<double>, dim3(grid_1d(n, kNT, 65536)), dim3(kNT), 0, s, n, row_ptr, col_idx,
+                           static_cast<const double *>(values.p), minv, bad);
     return hipGetLastError();
 }
 
 // Load this file's code object on the current device now (see preload_kernels).
 hipError_t preload_pcg() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_csr_diag_minv));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_csr_diag_minv<double>));
 }
 
 }  // namespace cgx

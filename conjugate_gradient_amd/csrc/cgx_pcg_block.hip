@@ -223,10 +223,13 @@ __global__ __launch_bounds__(kNT) void k_pcgb_update_xp_f64(int64_t n, double *_
 // whose column is (row / bs) * bs + j; +0.0 where there is none, and in the
 // rows past n of a short last block (its columns past n match no entry: the
 // indices passed cgx_csr_check).  D is block after block, row-major inside one.
+// VT = float (cgx_set_precond_block on a float-valued context): each entry is
+// widened exactly and the sums are the same double sums.
+template <class VT>
 __global__ __launch_bounds__(kNT) void k_csr_diag_blocks(int64_t n, int bs, int64_t rows,
                                                          const int64_t *__restrict__ row_ptr,
                                                          const int32_t *__restrict__ col_idx,
-                                                         const double *__restrict__ values, double *__restrict__ D) {
+                                                         const VT *__restrict__ values, double *__restrict__ D) {
 #pragma clang fp contract(off)
     constexpr int kMaxBs = 8;
     for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < rows; i += (int64_t)gridDim.x * kNT) {
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(kNT) void k_csr_diag_blocks(int64_t n, int bs, int6
             const int64_t e1 = row_ptr[i + 1];
             for (int64_t e = row_ptr[i]; e < e1; ++e) {
                 const int64_t c = (int64_t)col_idx[e] - row0;
-                const double v = values[e];
+                const double v = (double)values[e];
 #pragma unroll
                 for (int j = 0; j < kMaxBs; ++j) d[j] = (c == j) ? d[j] + v : d[j];
             }
@@ -325,18 +328,22 @@ hipError_t pcgb_update_xp_f64(int64_t n, double *x, double *p, const double *z, 
 }
 
 hipError_t csr_diag_blocks_f64(int64_t n, int bs, const int64_t *row_ptr, const int32_t *col_idx,
-                               const double *values, double *D, hipStream_t s) {
+                               CsrValues values, double *D, hipStream_t s) {
     if (bs < 2 || bs > kMaxPcBlock || n < 1) return hipErrorInvalidValue;
     const int64_t rows = (n + bs - 1) / bs * bs;
-    hipLaunchKernelGGL(k_csr_diag_blocks, dim3(grid_1d(rows, kNT, 65536)), dim3(kNT), 0, s, n, bs, rows, row_ptr,
-                       col_idx, values, D);
+    if (values.f32)
+        hipLaunchKernelGGL(k_csr_diag_blocks<float>, dim3(grid_1d(rows, kNT, 65536)), dim3(kNT), 0, s, n, bs, rows,
+                           row_ptr, col_idx, static_cast<const float *>(values.p), D);
+    else
+        hipLaunchKernelGGL(k_csr_diag_blocks<double>, dim3(grid_1d(rows, kNT, 65536)), dim3(kNT), 0, s, n, bs, rows,
+                           row_ptr, col_idx, static_cast<const double *>(values.p), D);
     return hipGetLastError();
 }
 
 // Load this file's code object on the current device now (see preload_kernels).
 hipError_t preload_pcg_block() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_csr_diag_blocks));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_csr_diag_blocks<double>));
 }
 
 }  // namespace cgx

@@ -831,7 +831,9 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
                   ((c->mode == M_LOCAL && c->xchg_kernels) ? CGX_PULL_ACTIVE : 0) |
                   ((c->fuse_combine || c->fuse_f32) ? CGX_FOLDED_ACTIVE : 0) | (c->halo_pull ? CGX_HALO_PULL_ACTIVE : 0) |
                   (c->pool ? CGX_THREADS_ACTIVE : 0) | (c->halo_overlap ? CGX_HALO_OVERLAP_ACTIVE : 0);
-    if (c->op == OP_CSR) info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0);
+    if (c->op == OP_CSR)
+        info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0) |
+                       (c->csr_f32 ? CGX_A_F32 : 0);  // float-valued since cgx_set_csr_f32
     info->elem_bytes = c->es;
     return CGX_OK;
 }

@@ -1,6 +1,6 @@
 // cgx_spmm.hip -- the sparse matVec of a cgx_create_csr_nrhs context: one pass
 // over a CSR matrix (row_ptr int64[n+1], col_idx int32[nnz], values
-// double[nnz]) multiplied by K vectors, Out_j = A V_j for j < nrhs, fp64.
+// double[nnz] or, on a float-valued context, float[nnz]) multiplied by K vectors, Out_j = A V_j for j < nrhs, fp64.
 //
 // The CSR-vector form of k_spmv_csr_f64 (cgx_spmv.hip): T consecutive lanes own
 // one row, a wave covers 64/T consecutive rows, waves walk the row groups with
@@ -22,7 +22,9 @@
 // stored order with one FMA each; the T partial sums are combined as
 // v[l] += v[l ^ o] for o = T/2, ..., 1.  Column j is therefore cgx_spmv_csr's
 // result on column j bit for bit at the same T, whatever K, the load policy,
-// the grid, or the trips a sub-lane keeps in flight.
+// the grid, or the trips a sub-lane keeps in flight.  Float-stored values
+// (VT = float) are widened with (double) before the same FMAs, as in
+// k_spmv_csr_f64: the double kernel's bits on (double)values[e].
 //
 // The kernel does not range-check col_idx: every host path checks the
 // structure first (cgx_csr_check).
@@ -42,10 +44,10 @@ namespace {
 template <int K>
 constexpr int kSpmmU = K == 8 ? 2 : 4;
 
-template <int T, int K, int NT>
+template <class VT, int T, int K, int NT>
 __global__ __launch_bounds__(kNT) void k_spmm_csr_f64(const int64_t *__restrict__ row_ptr,
                                                        const int32_t *__restrict__ col_idx,
-                                                       const double *__restrict__ values, int64_t rows, int nrhs,
+                                                       const VT *__restrict__ values, int64_t rows, int nrhs,
                                                        const double *__restrict__ V, int64_t ldv,
                                                        double *__restrict__ Out, int64_t ldo,
                                                        const double *__restrict__ pown, int64_t ldp, double *dot_out,
@@ -78,12 +80,13 @@ __global__ __launch_bounds__(kNT) void k_spmm_csr_f64(const int64_t *__restrict_
 #pragma unroll
         for (int j = 0; j < K; ++j) acc[j] = 0.0;
         for (int64_t k = s + sub; k < e; k += (int64_t)U * T) {
-            double a[U], x[U][K];
+            VT a[U];
+            double x[U][K];
             int32_t c[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool ok = k + (int64_t)u * T < e;
-                a[u] = ok ? load_a<NT>(values + k + (int64_t)u * T) : 0.0;
+                a[u] = ok ? load_a<NT>(values + k + (int64_t)u * T) : VT(0);
                 c[u] = ok ? load_a<NT>(col_idx + k + (int64_t)u * T) : -1;
             }
 #pragma unroll
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(kNT) void k_spmm_csr_f64(const int64_t *__restrict_
             for (int u = 0; u < U; ++u)
                 if (c[u] >= 0) {
 #pragma unroll
-                    for (int j = 0; j < K; ++j) acc[j] = __builtin_fma(a[u], x[u][j], acc[j]);
+                    for (int j = 0; j < K; ++j) acc[j] = __builtin_fma((double)a[u], x[u][j], acc[j]);
                 }
         }
 #pragma unroll
@@ -111,34 +114,55 @@ __global__ __launch_bounds__(kNT) void k_spmm_csr_f64(const int64_t *__restrict_
     ts_end(ts);
 }
 
-using SpmmFn = decltype(&k_spmm_csr_f64<8, 2, 1>);
+template <class VT>
+using SpmmFn = decltype(&k_spmm_csr_f64<VT, 8, 2, 1>);
 
-template <int K, int NT>
-SpmmFn pick_spmm_t(int T) {
+template <class VT, int K, int NT>
+SpmmFn<VT> pick_spmm_t(int T) {
     switch (T) {
-        case 2: return k_spmm_csr_f64<2, K, NT>;
-        case 4: return k_spmm_csr_f64<4, K, NT>;
-        case 8: return k_spmm_csr_f64<8, K, NT>;
-        case 16: return k_spmm_csr_f64<16, K, NT>;
-        case 32: return k_spmm_csr_f64<32, K, NT>;
-        case 64: return k_spmm_csr_f64<64, K, NT>;
+        case 2: return k_spmm_csr_f64<VT, 2, K, NT>;
+        case 4: return k_spmm_csr_f64<VT, 4, K, NT>;
+        case 8: return k_spmm_csr_f64<VT, 8, K, NT>;
+        case 16: return k_spmm_csr_f64<VT, 16, K, NT>;
+        case 32: return k_spmm_csr_f64<VT, 32, K, NT>;
+        case 64: return k_spmm_csr_f64<VT, 64, K, NT>;
         default: return nullptr;
     }
 }
-template <int NT>
-SpmmFn pick_spmm_nt(int K, int T) {
-    return K == 2 ? pick_spmm_t<2, NT>(T) : K == 4 ? pick_spmm_t<4, NT>(T) : K == 8 ? pick_spmm_t<8, NT>(T) : nullptr;
+template <class VT, int NT>
+SpmmFn<VT> pick_spmm_nt(int K, int T) {
+    return K == 2   ? pick_spmm_t<VT, 2, NT>(T)
+           : K == 4 ? pick_spmm_t<VT, 4, NT>(T)
+           : K == 8 ? pick_spmm_t<VT, 8, NT>(T)
+                    : nullptr;
 }
-// the instantiated plan's kernel, or nullptr: K vectors, T lanes per row, load policy 2 or 8
-SpmmFn pick_spmm(int K, int T, int nt) {
-    return nt == 8 ? pick_spmm_nt<1>(K, T) : nt == 2 ? pick_spmm_nt<0>(K, T) : nullptr;
+// the instantiated plan's kernel, or nullptr: K vectors, T lanes per row, load policy 2 or 8;
+// the same (K, T, policy) list for double (VT = double) and float values
+template <class VT>
+SpmmFn<VT> pick_spmm(int K, int T, int nt) {
+    return nt == 8 ? pick_spmm_nt<VT, 1>(K, T) : nt == 2 ? pick_spmm_nt<VT, 0>(K, T) : nullptr;
+}
+const void *spmm_fn(int K, int T, int nt, bool f32) {
+    return f32 ? reinterpret_cast<const void *>(pick_spmm<float>(K, T, nt))
+               : reinterpret_cast<const void *>(pick_spmm<double>(K, T, nt));
+}
+
+template <class VT>
+hipError_t launch_spmm(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const void *values,
+                       int64_t rows, int nrhs, const double *V, int64_t ldv, double *Out, int64_t ldo,
+                       const double *pown, int64_t ldp, double *dot_out, const RedWs &ws, hipStream_t s,
+                       const int64_t *gate, int64_t *ts) {
+    hipLaunchKernelGGL(pick_spmm<VT>(pl.nrhs, 64 / pl.R, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, row_ptr, col_idx,
+                       static_cast<const VT *>(values), rows, nrhs, V, ldv, Out, ldo, pown, ldp, dot_out, ws.partials,
+                       ws.tickets + TN_MATVEC, gate, ts);
+    return hipGetLastError();
 }
 
 }  // namespace
 
-bool spmm_csr_plan_ok(int K, int T, int nt) { return pick_spmm(K, T, nt) != nullptr; }
+bool spmm_csr_plan_ok(int K, int T, int nt) { return pick_spmm<double>(K, T, nt) != nullptr; }
 
-MatvecPlan plan_spmm_csr(int device, int64_t rows, int64_t nnz, int K, int T, int nt, int blocks_per_cu) {
+MatvecPlan plan_spmm_csr(int device, int64_t rows, int64_t nnz, int K, int T, int nt, int blocks_per_cu, bool f32) {
     MatvecPlan pl;
     pl.csr = 1;
     pl.nrhs = K;
@@ -177,12 +201,11 @@ MatvecPlan plan_spmm_csr(int device, int64_t rows, int64_t nnz, int K, int T, in
     if (T > 0) pl.R = spmm_csr_plan_ok(K, T, 8) ? 64 / T : 0;
     if (nt >= 0) pl.nt = nt;
     if (pl.R < 1 || !spmm_csr_plan_ok(K, 64 / pl.R, pl.nt)) pl.R = 64 / t, pl.nt = 2;
-    pl.blocks = plan_grid(reinterpret_cast<const void *>(pick_spmm(K, 64 / pl.R, pl.nt)), device, rows, pl.R, 8,
-                          "CGX_SPMM_PLAN", blocks_per_cu);
+    pl.blocks = plan_grid(spmm_fn(K, 64 / pl.R, pl.nt, f32), device, rows, pl.R, 8, "CGX_SPMM_PLAN", blocks_per_cu);
     return pl;
 }
 
-hipError_t spmm_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+hipError_t spmm_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                         int64_t rows, int nrhs, const double *V, int64_t ldv, double *Out, int64_t ldo,
                         const double *pown, int64_t ldp, double *dot_out, const RedWs &ws, hipStream_t s,
                         const int64_t *gate, int64_t *ts) {
@@ -190,15 +213,16 @@ hipError_t spmm_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int3
     if (nrhs < 1 || nrhs > kMaxNrhs || !pl.csr || pl.nrhs != nrhs_width(nrhs) || pl.R < 1 || pl.R > 32 ||
         !spmm_csr_plan_ok(pl.nrhs, 64 / pl.R, pl.nt) || pl.blocks < 1 || pl.blocks > kMaxRedBlocks)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pick_spmm(pl.nrhs, 64 / pl.R, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, row_ptr, col_idx, values,
-                       rows, nrhs, V, ldv, Out, ldo, pown, ldp, dot_out, ws.partials, ws.tickets + TN_MATVEC, gate, ts);
-    return hipGetLastError();
+    return values.f32 ? launch_spmm<float>(pl, row_ptr, col_idx, values.p, rows, nrhs, V, ldv, Out, ldo, pown, ldp,
+                                           dot_out, ws, s, gate, ts)
+                      : launch_spmm<double>(pl, row_ptr, col_idx, values.p, rows, nrhs, V, ldv, Out, ldo, pown, ldp,
+                                            dot_out, ws, s, gate, ts);
 }
 
 // Load this file's code object on the current device now (see preload_kernels).
 hipError_t preload_spmm() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_spmm_csr_f64<8, 2, 1>));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_spmm_csr_f64<double, 8, 2, 1>));
 }
 
 }  // namespace cgx

@@ -1,5 +1,6 @@
 // cgx_spmv.hip -- the sparse matVec of a cgx_create_csr context: A in CSR
-// storage (row_ptr int64[n+1], col_idx int32[nnz], values double[nnz]), fp64.
+// storage (row_ptr int64[n+1], col_idx int32[nnz], values double[nnz] or, on a
+// float-valued context, float[nnz]), fp64.
 //
 // CSR-vector form.  T consecutive lanes own one row (T = 2 .. 64), so a wave
 // covers 64/T consecutive rows and its loads of values and col_idx are
@@ -15,6 +16,12 @@
 // v[l] += v[l ^ o] for o = T/2, ..., 1.  Columns need not be sorted and a
 // duplicate column is two terms.  A row's sum depends on T only: not on the
 // load policy, the grid, or where the row falls in a wave.
+//
+// Float-stored values (VT = float, cgx_set_csr_f32): an entry is loaded as 4
+// bytes through the same policy and widened with (double), which is exact,
+// denormals included; the FMA, its order and everything after it are the double
+// kernel's.  So the row sum is the double kernel's on (double)values[e] bit for
+// bit, and an entry streams 8 bytes in place of 12.
 //
 // No load balancing: a row of length L costs ceil(L / T) trips
 // of its T lanes while the wave's other rows wait.
@@ -33,10 +40,10 @@ namespace {
 // order.  A trip past the row's end loads nothing and adds nothing.
 constexpr int kSpmvU = 4;
 
-template <int T, int NT>
+template <class VT, int T, int NT>
 __global__ __launch_bounds__(kNT) void k_spmv_csr_f64(const int64_t *__restrict__ row_ptr,
                                                        const int32_t *__restrict__ col_idx,
-                                                       const double *__restrict__ values, int64_t rows,
+                                                       const VT *__restrict__ values, int64_t rows,
                                                        const double *__restrict__ v, double *__restrict__ out,
                                                        const double *__restrict__ pown, double *dot_out,
                                                        double *partials, unsigned *ticket, const int64_t *gate,
@@ -60,19 +67,20 @@ __global__ __launch_bounds__(kNT) void k_spmv_csr_f64(const int64_t *__restrict_
         }
         double acc = 0.0;
         for (int64_t k = s + sub; k < e; k += (int64_t)kSpmvU * T) {
-            double a[kSpmvU], x[kSpmvU];
+            VT a[kSpmvU];
+            double x[kSpmvU];
             int32_t c[kSpmvU];
 #pragma unroll
             for (int u = 0; u < kSpmvU; ++u) {
                 const bool ok = k + (int64_t)u * T < e;
-                a[u] = ok ? load_a<NT>(values + k + (int64_t)u * T) : 0.0;
+                a[u] = ok ? load_a<NT>(values + k + (int64_t)u * T) : VT(0);
                 c[u] = ok ? load_a<NT>(col_idx + k + (int64_t)u * T) : -1;
             }
 #pragma unroll
             for (int u = 0; u < kSpmvU; ++u) x[u] = c[u] >= 0 ? v[c[u]] : 0.0;
 #pragma unroll
             for (int u = 0; u < kSpmvU; ++u)
-                if (c[u] >= 0) acc = __builtin_fma(a[u], x[u], acc);
+                if (c[u] >= 0) acc = __builtin_fma((double)a[u], x[u], acc);
         }
 #pragma unroll
         for (int o = T / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
@@ -82,28 +90,47 @@ __global__ __launch_bounds__(kNT) void k_spmv_csr_f64(const int64_t *__restrict_
     ts_end(ts);
 }
 
-using SpmvFn = decltype(&k_spmv_csr_f64<8, 1>);
+template <class VT>
+using SpmvFn = decltype(&k_spmv_csr_f64<VT, 8, 1>);
 
-template <int NT>
-SpmvFn pick_spmv_nt(int T) {
+template <class VT, int NT>
+SpmvFn<VT> pick_spmv_nt(int T) {
     switch (T) {
-        case 2: return k_spmv_csr_f64<2, NT>;
-        case 4: return k_spmv_csr_f64<4, NT>;
-        case 8: return k_spmv_csr_f64<8, NT>;
-        case 16: return k_spmv_csr_f64<16, NT>;
-        case 32: return k_spmv_csr_f64<32, NT>;
-        case 64: return k_spmv_csr_f64<64, NT>;
+        case 2: return k_spmv_csr_f64<VT, 2, NT>;
+        case 4: return k_spmv_csr_f64<VT, 4, NT>;
+        case 8: return k_spmv_csr_f64<VT, 8, NT>;
+        case 16: return k_spmv_csr_f64<VT, 16, NT>;
+        case 32: return k_spmv_csr_f64<VT, 32, NT>;
+        case 64: return k_spmv_csr_f64<VT, 64, NT>;
         default: return nullptr;
     }
 }
-// the instantiated plan's kernel, or nullptr: T lanes per row, load policy 2 or 8
-SpmvFn pick_spmv(int T, int nt) { return nt == 8 ? pick_spmv_nt<1>(T) : nt == 2 ? pick_spmv_nt<0>(T) : nullptr; }
+// the instantiated plan's kernel, or nullptr: T lanes per row, load policy 2 or 8;
+// the same (T, policy) list for double (VT = double) and float values
+template <class VT>
+SpmvFn<VT> pick_spmv(int T, int nt) {
+    return nt == 8 ? pick_spmv_nt<VT, 1>(T) : nt == 2 ? pick_spmv_nt<VT, 0>(T) : nullptr;
+}
+const void *spmv_fn(int T, int nt, bool f32) {
+    return f32 ? reinterpret_cast<const void *>(pick_spmv<float>(T, nt))
+               : reinterpret_cast<const void *>(pick_spmv<double>(T, nt));
+}
+
+template <class VT>
+hipError_t launch_spmv(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const void *values,
+                       int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
+                       const RedWs &ws, hipStream_t s, const int64_t *gate, int64_t *ts) {
+    hipLaunchKernelGGL(pick_spmv<VT>(64 / pl.R, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, row_ptr, col_idx,
+                       static_cast<const VT *>(values), rows, v, out, pown, dot_out, ws.partials,
+                       ws.tickets + T_MATVEC, gate, ts);
+    return hipGetLastError();
+}
 
 }  // namespace
 
-bool spmv_csr_plan_ok(int T, int nt) { return pick_spmv(T, nt) != nullptr; }
+bool spmv_csr_plan_ok(int T, int nt) { return pick_spmv<double>(T, nt) != nullptr; }
 
-MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T, int nt, int blocks_per_cu) {
+MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T, int nt, int blocks_per_cu, bool f32) {
     MatvecPlan pl;
     pl.csr = 1;
     pl.U = 1;
@@ -139,26 +166,24 @@ MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T, int nt, i
     if (T > 0) pl.R = spmv_csr_plan_ok(T, 8) ? 64 / T : 0;
     if (nt >= 0) pl.nt = nt;
     if (pl.R < 1 || !spmv_csr_plan_ok(64 / pl.R, pl.nt)) pl.R = 64 / t, pl.nt = 2;
-    pl.blocks = plan_grid(reinterpret_cast<const void *>(pick_spmv(64 / pl.R, pl.nt)), device, rows, pl.R, 8,
-                          "CGX_SPMV_PLAN", blocks_per_cu);
+    pl.blocks = plan_grid(spmv_fn(64 / pl.R, pl.nt, f32), device, rows, pl.R, 8, "CGX_SPMV_PLAN", blocks_per_cu);
     return pl;
 }
 
-hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                         int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
                         const RedWs &ws, hipStream_t s, const int64_t *gate, int64_t *ts) {
     if (rows <= 0) return hipSuccess;
     if (!pl.csr || pl.R < 1 || pl.R > 32 || !spmv_csr_plan_ok(64 / pl.R, pl.nt) || pl.blocks < 1)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pick_spmv(64 / pl.R, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, row_ptr, col_idx, values, rows,
-                       v, out, pown, dot_out, ws.partials, ws.tickets + T_MATVEC, gate, ts);
-    return hipGetLastError();
+    return values.f32 ? launch_spmv<float>(pl, row_ptr, col_idx, values.p, rows, v, out, pown, dot_out, ws, s, gate, ts)
+                      : launch_spmv<double>(pl, row_ptr, col_idx, values.p, rows, v, out, pown, dot_out, ws, s, gate, ts);
 }
 
 // Load this file's code object on the current device now (see preload_kernels).
 hipError_t preload_spmv() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_spmv_csr_f64<8, 1>));
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_spmv_csr_f64<double, 8, 1>));
 }
 
 }  // namespace cgx

@@ -238,6 +238,33 @@
  *       (CGX_ERR_ARG: batched CG has no preconditioned update kernels);
  *       cgx_solve_begin, cgx_solve and cgx_residual_norms before the first
  *       cgx_set_csr (CGX_ERR_STATE).
+ *   - Float-stored values (cgx_set_csr_f32, on a cgx_create_csr or
+ *     cgx_create_csr_nrhs context): the values go up and stay on the device as
+ *     float[nnz], which is what the reference holds on every input path; an
+ *     entry then streams 8 bytes per product in place of 12.  There is no fp32
+ *     arithmetic: every kernel widens a value with (double), which is exact
+ *     (denormals included), and then does the double-valued kernel's fp64
+ *     operations in the same order.
+ *     - The contract: a float-valued context gives, bit for bit, what a
+ *       double-valued context gives on (double)values[e] -- the row sums of the
+ *       SpMV and the SpMM at the same T, the fused p.Ap on the same grid,
+ *       1 / diag(A), the diagonal blocks and their inverses, and so x, the
+ *       loop count and r.r in every host form, with every preconditioner kind.
+ *     - The context is float-valued until the next cgx_set_csr (double-valued
+ *       again) or cgx_set_csr_f32.  cgx_set_csr_f32 is cgx_set_csr otherwise:
+ *       the same checks in the same order and the same refusals, nothing
+ *       uploaded when one fails (the earlier matrix, its value type and its
+ *       preconditioner stay), a solve in progress ended, preconditioning off,
+ *       and a new default plan unless the caller chose one (the default T rule
+ *       is the same for both value types).
+ *     - cgx_get_info: flags carries CGX_A_F32 (reported) while the context is
+ *       float-valued; elem_bytes stays 8.  CGX_A_F32 at cgx_create_csr stays
+ *       refused: the value type comes with the matrix, not with the context.
+ *     - The allocation is not halved: the floats live in the context's value
+ *       buffer, which has room for nnz doubles.  A constructor that allocates
+ *       4 bytes per entry is not built.
+ *     - Kernel-level: cgx_spmv_csr_f32, cgx_spmm_csr_f32.  cgx_csr_diag_blocks
+ *       takes double values only.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -265,7 +292,9 @@ extern "C" {
                            and the reported bit CGX_PRECOND_ACTIVE; likewise
                            cgx_create_csr_nrhs and cgx_spmm_csr (new functions only, no new bit);
                            likewise cgx_set_precond_block and its entry points and the kind
-                           CGX_PC_BLOCK (new functions only, no new bit) */
+                           CGX_PC_BLOCK (new functions only, no new bit); likewise
+                           cgx_set_csr_f32, cgx_spmv_csr_f32 and cgx_spmm_csr_f32 (new functions
+                           only; CGX_A_F32 is also reported by a float-valued CSR context) */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -592,6 +621,10 @@ int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags)
 /* Host arrays (row_ptr[n] entries, at most the context's nnz); runs cgx_csr_check first and
  * uploads nothing when it fails (an earlier matrix stays as it was).  Ends a solve in progress. */
 int cgx_set_csr(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, const double *values);
+/* cgx_set_csr with float values, which stay float on the device (see "Float-stored values"
+ * above): the context gives the bits a double-valued one gives on (double)values[e].  The same
+ * checks, refusals and effects as cgx_set_csr; a failed call also leaves the value type as it was. */
+int cgx_set_csr_f32(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, const float *values);
 /* One GPU, fp64: nrhs (1..CGX_MAX_NRHS) systems A x_j = b_j on one CSR matrix with room for
  * nnz entries, solved together, one read of the CSR arrays per iteration.
  * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
@@ -745,6 +778,10 @@ int cgx_matvec_nrhs(const void *A, int64_t lda, int64_t rows, int64_t cols, int 
  * T comes from CGX_SPMV_PLAN="T=..,nt=..,bpc=.." (default T = 8). */
 int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
                  const void *values, const void *v, void *out, void *stream);
+/* cgx_spmv_csr on float values (device pointer), widened exactly: the bits cgx_spmv_csr gives on
+ * (double)values[e] at the same T.  Plan from CGX_SPMV_PLAN as above. */
+int cgx_spmv_csr_f32(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
+                     const float *values, const void *v, void *out, void *stream);
 /* Kernel-level, device pointers: Out[j*ldo + i] = sum_e values[e] * V[j*ldv + col_idx[e]],
  * j < nrhs.  Column j is cgx_spmv_csr's result on column j bit for bit at the same T.
  * The indices must have passed cgx_csr_check.  T comes from
@@ -752,6 +789,11 @@ int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *co
 int cgx_spmm_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
                  const void *values, int nrhs, const void *V, int64_t ldv,
                  void *Out, int64_t ldo, void *stream);
+/* cgx_spmm_csr on float values (device pointer), widened exactly: the bits cgx_spmm_csr gives on
+ * (double)values[e] at the same T.  Plan from CGX_SPMM_PLAN as above. */
+int cgx_spmm_csr_f32(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
+                     const float *values, int nrhs, const void *V, int64_t ldv,
+                     void *Out, int64_t ldo, void *stream);
 /* vecVec: *out_dev = a . b */
 int cgx_dot(int dtype, int64_t n, const void *a, const void *b, void *out_dev, void *stream);
 /* residual x2 + vecVec: r = b - Ax; p = b - Ax; *rr_dev = r.r (rr_dev may be NULL) */
