@@ -39,6 +39,7 @@ __all__ = [
     "device_pci_bus_id", "device_link",
     "CGX_MAX_NRHS", "matVec_nrhs",
     "CGX_CSR_ACTIVE", "spmv_csr", "spmm_csr",
+    "CGX_CSR_HALO_ACTIVE", "csr_halo_counts", "csr_halo_list", "gather_indexed",
     "CGX_PRECOND_ACTIVE", "PRECOND_KINDS", "PC_BLOCK", "CGX_MAX_PC_BLOCK", "csr_diag_blocks", "precond_block_invert",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
     "count_text", "read_dims", "device_count", "get_unique_id", "DeviceArray",
@@ -68,6 +69,8 @@ CGX_THREADS_ACTIVE = 0x2000000
 CGX_HALO_OVERLAP_ACTIVE = 0x4000000
 CGX_CSR_ACTIVE = 0x8000000  # reported in info.flags: a cgx_create_csr context (Solver(n, csr_nnz=...))
 CGX_PRECOND_ACTIVE = 0x10000000  # reported in info.flags: a CSR context iterating with a diagonal preconditioner
+# reported in info.flags: a CSR solver over several row blocks (devices=) exchanging p by index lists
+CGX_CSR_HALO_ACTIVE = 0x20000000
 # cgx_set_precond's kinds, CGX_PC_NONE / CGX_PC_JACOBI / CGX_PC_DIAG (include/cgx.h), by the names Solver.precond
 # reports.  Kept out of the CGX_* names: those are the flag words, and a kind is not a bit of one.
 PRECOND_KINDS = {"none": 0, "jacobi": 1, "diag": 2}
@@ -189,6 +192,11 @@ def lib() -> ctypes.CDLL:
         "cgx_spmv_csr": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_spmv_csr_f32": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_create_csr_nrhs": ([pctx, i64, i64, i32, i32, i32], i32),
+        "cgx_create_csr_multi": ([pctx, i64, i64, i32, ctypes.POINTER(i32), i32], i32),
+        "cgx_csr_halo_counts": ([i64, i32, vp, vp, vp], i32),
+        "cgx_csr_halo_list": ([i64, i32, vp, vp, i32, i32, vp], i32),
+        "cgx_get_csr_halo": ([vp, vp], i32),
+        "cgx_gather_indexed": ([vp, vp, i64, vp, vp], i32),
         "cgx_spmm_csr": ([i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp], i32),
         "cgx_spmm_csr_f32": ([i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp], i32),
         "cgx_precond_diag_check": ([i64, vp], i32),
@@ -514,6 +522,60 @@ def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int,
             d.free()
 
 
+def _halo_structure(what: str, indptr, indices, nshards):
+    """(n, indptr int64, indices int32) of a host-only exchange-plan call."""
+    rp = np.ascontiguousarray(indptr, np.int64)
+    ci = np.ascontiguousarray(indices, np.int32)
+    _need(rp.ndim == 1 and ci.ndim == 1 and rp.size >= 2, f"{what}: indptr needs n + 1 >= 2 entries")
+    _need(isinstance(nshards, (int, np.integer)) and not isinstance(nshards, bool),
+          f"{what}: nshards must be an integer (got {nshards!r})")
+    # the library reads indices[0 .. indptr[n]): a longer claim than the array is caught here
+    _need(int(rp[-1]) <= ci.size, f"{what}: indptr[n] = {int(rp[-1])} but {ci.size} indices")
+    return rp.size - 1, rp, ci
+
+
+def csr_halo_counts(indptr, indices, nshards: int) -> np.ndarray:
+    """cgx_csr_halo_counts (host only, no GPU): the exchange plan of a CSR structure over ``nshards`` equal row
+    blocks, an ``(nshards, nshards)`` int64 array whose entry ``[d, q]`` is how many distinct columns of block q's
+    row range occur in block d's rows (0 on the diagonal) -- the entries of p block d pulls from block q per
+    iteration.  CgxError(-4) when the structure fails cgx_csr_check or nshards does not divide n."""
+    n, rp, ci = _halo_structure("csr_halo_counts", indptr, indices, nshards)
+    out = np.zeros((max(int(nshards), 0), max(int(nshards), 0)), np.int64)
+    _check(lib().cgx_csr_halo_counts(n, int(nshards), _ptr(rp), _ptr(ci), _ptr(out)), "cgx_csr_halo_counts")
+    return out
+
+
+def csr_halo_list(indptr, indices, nshards: int, dst: int, src: int) -> np.ndarray:
+    """cgx_csr_halo_list (host only): the offsets into block ``src`` (column minus src's first row) that block
+    ``dst``'s rows name, ascending, each once (int32)."""
+    n, rp, ci = _halo_structure("csr_halo_list", indptr, indices, nshards)
+    counts = csr_halo_counts(rp, ci, nshards)  # the list's length; raises on a bad structure or partition
+    _need(all(isinstance(v, (int, np.integer)) for v in (dst, src)), "csr_halo_list: dst and src must be integers")
+    _need(0 <= dst < nshards and 0 <= src < nshards, f"csr_halo_list: blocks ({dst}, {src}) outside [0, {nshards})")
+    out = np.empty(int(counts[dst, src]), np.int32)
+    _check(lib().cgx_csr_halo_list(n, int(nshards), _ptr(rp), _ptr(ci), int(dst), int(src), _ptr(out)),
+           "cgx_csr_halo_list")
+    return out
+
+
+def gather_indexed(src: DeviceArray, idx: DeviceArray, dst: DeviceArray, count: int | None = None) -> None:
+    """cgx_gather_indexed (k_gather_indexed alone): ``dst[idx[e]] = src[idx[e]]`` for e < count (float64 arrays,
+    int32 ``idx`` with every value once).  The kernel does not range-check, so the indices are read back and
+    checked against both arrays here before the launch, and the device is synchronised after it: a call for tests
+    of the kernel's result, not one to time (tools/csr_multi_ab.py times the exchange inside a context)."""
+    count = idx.count if count is None else int(count)
+    _need(src.dtype == np.float64 and dst.dtype == np.float64 and idx.dtype == np.int32,
+          "gather_indexed: float64 src and dst, int32 idx")
+    _need(0 <= count <= idx.count, f"gather_indexed: count {count} outside [0, {idx.count}]")
+    if count == 0:
+        return
+    ix = idx.to_host()[:count]
+    _need(int(ix.min()) >= 0 and int(ix.max()) < min(src.count, dst.count),
+          f"gather_indexed: an index outside [0, {min(src.count, dst.count)})")
+    _check(lib().cgx_gather_indexed(src.ptr, idx.ptr, count, dst.ptr, None), "cgx_gather_indexed")
+    _check(lib().cgx_dev_synchronize(), "cgx_dev_synchronize")
+
+
 def _block_count(n: int, bs: int) -> int:
     return (n + bs - 1) // bs
 
@@ -613,7 +675,9 @@ class Solver:
     (or build the solver with :meth:`from_csr`), b and x through ``set_rows``
     / ``set_x`` / ``fill``.  Several right-hand sides on a CSR matrix
     (cgx_create_csr_nrhs) are spelled ``Solver.csr(n, nnz, nrhs=K)`` or
-    ``Solver.from_csr(..., nrhs=K)``; ``Solver(n, csr_nnz=..., nrhs=...)`` raises."""
+    ``Solver.from_csr(..., nrhs=K)``; ``Solver(n, csr_nnz=..., nrhs=...)`` raises.  A sparse A over
+    several row blocks (cgx_create_csr_multi) is spelled ``Solver.csr(n, nnz, devices=[...])`` or
+    ``Solver.from_csr(..., devices=[...])``; ``Solver(n, csr_nnz=..., devices=...)`` raises."""
 
     def __init__(self, n: int, *, flags: int = CGX_F64, device: int = 0, devices=None,
                  rank: int | None = None, nranks: int | None = None, unique_id: bytes | None = None,
@@ -671,11 +735,31 @@ class Solver:
         self._h = h.value
 
     @classmethod
-    def csr(cls, n: int, nnz: int, *, nrhs: int | None = None, device: int = 0, flags: int = CGX_F64) -> "Solver":
+    def csr(cls, n: int, nnz: int, *, nrhs: int | None = None, device: int = 0, flags: int = CGX_F64,
+            devices=None) -> "Solver":
         """An empty CSR solver with room for ``nnz`` entries (the matrix goes in through
         :meth:`set_csr`).  ``nrhs=K`` (cgx_create_csr_nrhs): K systems on the one matrix solved
         together, one read of the CSR arrays per iteration; b and x are then ``(K, n)`` arrays as
-        on a dense ``nrhs`` solver.  Without ``nrhs`` it is ``Solver(n, csr_nnz=nnz)``."""
+        on a dense ``nrhs`` solver.  ``devices=[...]`` (cgx_create_csr_multi): ``len(devices)`` equal
+        row blocks in this process, one per listed device (a device may repeat), every block with
+        room for ``nnz`` entries -- a safe bound; not with ``nrhs``.  Without either it is
+        ``Solver(n, csr_nnz=nnz)``."""
+        if devices is not None:  # checked before any C call
+            _need(nrhs is None, "Solver.csr: several right-hand sides run on one GPU (not with devices=)")
+            _need(device == 0, "Solver.csr: devices= lists every block's device (not with device=)")
+            devs = [int(d) for d in devices]
+            _need(isinstance(nnz, (int, np.integer)) and nnz >= 0,
+                  f"Solver.csr: nnz must be an integer >= 0 (got {nnz})")
+            _need(isinstance(n, (int, np.integer)) and n >= 1, f"Solver.csr: n must be an integer >= 1 (got {n})")
+            h = ctypes.c_void_p()
+            arr = (ctypes.c_int * max(len(devs), 1))(*devs)
+            rc = lib().cgx_create_csr_multi(ctypes.byref(h), int(n), int(nnz), len(devs), arr, flags)
+            _check(rc, "cgx_create_csr_multi")
+            s = cls.__new__(cls)  # the fields __init__ sets
+            s.nrhs, s.csr_nnz, s.poisson_m, s.devices = None, int(nnz), None, devs
+            s.n, s.flags, s.dtype = int(n), flags, _dtype(flags)
+            s._h = h.value
+            return s
         if nrhs is None:
             return cls(n, flags=flags, device=device, csr_nnz=nnz)
         _need(isinstance(nrhs, (int, np.integer)) and 1 <= nrhs <= CGX_MAX_NRHS,
@@ -693,16 +777,26 @@ class Solver:
 
     @classmethod
     def from_csr(cls, indptr, indices=None, data=None, *, device: int = 0, flags: int = CGX_F64,
-                 precond=None, nrhs: int | None = None, a_f32: bool = False) -> "Solver":
+                 precond=None, nrhs: int | None = None, a_f32: bool = False, devices=None) -> "Solver":
         """A CSR solver sized for this matrix, with the matrix set (b = 0, x0 = 0)
         and, with ``precond`` ("jacobi", an array or ``("block", bs)``), its preconditioner (:meth:`set_precond`).
         ``nrhs=K``: K systems on the matrix solved together (:meth:`csr`; no preconditioner).
-        ``a_f32=True``: float-stored values (:meth:`set_csr`)."""
+        ``a_f32=True``: float-stored values (:meth:`set_csr`).
+        ``devices=[...]``: equal row blocks over the listed devices (:meth:`csr`), each with room for the
+        largest block's entries; no preconditioner and no ``nrhs``."""
         a_f32 = _a_f32_flag("from_csr", a_f32)
         rp, ci, va = _csr_arrays(indptr, indices, data, a_f32)
         _need(rp.size >= 2, "from_csr: indptr needs n + 1 >= 2 entries")
         _need(nrhs is None or precond is None, "from_csr: no preconditioner with several right-hand sides")
-        s = cls.csr(rp.size - 1, int(ci.size), nrhs=nrhs, device=device, flags=flags)
+        nnz = int(ci.size)
+        if devices is not None:  # checked before any C call
+            _need(nrhs is None and precond is None,
+                  "from_csr: row blocks (devices=) take no preconditioner and one right-hand side")
+            P, n = len(devices), rp.size - 1
+            if P >= 1 and n % P == 0:  # the largest block's exact count; any other partition the library refuses
+                nnz = int(np.max(np.diff(rp[::n // P]), initial=0))
+                nnz = max(nnz, 0)
+        s = cls.csr(rp.size - 1, nnz, nrhs=nrhs, device=device, flags=flags, devices=devices)
         try:
             s.set_csr(rp, ci, va, a_f32=a_f32)
             if precond is not None:
@@ -725,11 +819,24 @@ class Solver:
         _need(getattr(self, "csr_nnz", None) is not None, "set_csr: the solver was not created with csr_nnz=")
         rp, ci, va = _csr_arrays(indptr, indices, data, a_f32)
         _need(rp.size == self.n + 1, f"set_csr: indptr has {rp.size} entries, n + 1 = {self.n + 1} needed")
-        _need(ci.size <= self.csr_nnz, f"set_csr: {ci.size} entries, the solver has room for {self.csr_nnz}")
+        if getattr(self, "devices", None) is None:  # row blocks: the room is per block, and the library checks it
+            _need(ci.size <= self.csr_nnz, f"set_csr: {ci.size} entries, the solver has room for {self.csr_nnz}")
+        else:
+            _need(int(rp[-1]) <= ci.size, f"set_csr: indptr[n] = {int(rp[-1])} but {ci.size} indices")
         if a_f32:
             _check(lib().cgx_set_csr_f32(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr_f32")
         else:
             _check(lib().cgx_set_csr(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr")
+
+    def csr_halo(self) -> np.ndarray:
+        """cgx_get_csr_halo: the ``(nshards, nshards)`` exchange counts in use on a CSR solver over row blocks
+        (``devices=``) -- entry ``[d, q]`` is how many entries of p block d pulls from block q per iteration;
+        :func:`csr_halo_counts` of the matrix that was set.  CgxError(-6) before the first :meth:`set_csr`,
+        CgxError(-1) on any other solver."""
+        P = len(getattr(self, "devices", None) or [0])
+        out = np.zeros((P, P), np.int64)
+        _check(lib().cgx_get_csr_halo(self._h, _ptr(out)), "cgx_get_csr_halo")
+        return out
 
     def set_precond(self, precond) -> None:
         """Diagonal preconditioning of a ``csr_nnz`` solver: ``"jacobi"`` (1 / diag(A),

@@ -19,6 +19,13 @@
 // A's bs x bs diagonal blocks there instead (extracted on the device, inverted
 // on the host by cgx_pcblock.hip, or the caller's), and one more n-vector z;
 // the iteration then runs cgx_pcg_block.hip's kernels.
+//
+// cgx_create_csr_multi (cgx_setup.hip) puts the matrix on several row blocks of
+// one process: cgx_set_csr splits the host arrays by rows (csr_upload_blocks)
+// and builds, per block, the lists of the entries of p it needs from every
+// other block (halo_block; cgx_csr_halo_counts / cgx_csr_halo_list run the same
+// builder without a GPU).  The iteration is cgx_create_multi's with the SpMV
+// per block and gather_indexed (cgx_vector.hip) as the exchange of p.
 #include "cgx_ctx.h"
 
 namespace cgxh {
@@ -34,12 +41,61 @@ int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
     if (!r_ok || U != 1 || !spmv_csr_plan_ok(64 / R, nt))
         return fail(CGX_ERR_ARG, "cgx_create_csr context: rows_per_wave (64 / T) must be 1, 2, 4, 8, 16 or 32, "
                                  "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
-    Shard &s = c->sh[0];
-    TRY(set_dev(s));
-    s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu,
-                           c->csr_f32);
+    for (auto &s : c->sh) {  // one T for every row block, each block's grid from its own rows
+        TRY(set_dev(s));
+        s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu,
+                               c->csr_f32);
+    }
     c->csr_plan_user = true;
     return CGX_OK;
+}
+
+// ---- the exchange plan of a sparse A over equal row blocks -------------------------
+// Block d (rows [d nloc, (d + 1) nloc)) needs, of block q's slice of p, the
+// entries its col_idx names: one pass over the block's col_idx marks them, one
+// scan of the marks between the lowest and the highest column named writes
+// them out in ascending order, source after source (nothing is sorted).
+// off[q] .. off[q + 1] is source q's list in `lists` (offsets into q's
+// slice); the own block's list is empty.  `mark` is n zero
+// bytes on entry and on return.  lists == nullptr: the counts only.
+static void halo_block(int64_t n, int S, const int64_t *row_ptr, const int32_t *col_idx, int d,
+                       std::vector<uint8_t> &mark, int64_t *off, std::vector<int32_t> *lists) {
+    const int64_t nloc = n / S, lo = (int64_t)d * nloc, hi = lo + nloc;
+    int64_t cmin = n, cmax = -1;  // the columns the block names: the scan stays inside them
+    for (int64_t e = row_ptr[lo]; e < row_ptr[hi]; ++e) {
+        const int64_t c = col_idx[e];
+        mark[c] = 1;
+        cmin = std::min(cmin, c);
+        cmax = std::max(cmax, c);
+    }
+    off[0] = 0;
+    if (lists) lists->clear();
+    for (int q = 0; q < S; ++q) {
+        int64_t cnt = 0;
+        uint8_t *m = mark.data() + (int64_t)q * nloc;
+        const int64_t j0 = std::max<int64_t>(0, cmin - (int64_t)q * nloc);
+        const int64_t j1 = std::min<int64_t>(nloc, cmax + 1 - (int64_t)q * nloc);
+        for (int64_t j = j0; j < j1; ++j) {
+            if (!m[j]) continue;
+            m[j] = 0;
+            if (q == d) continue;
+            ++cnt;
+            if (lists) lists->push_back((int32_t)j);
+        }
+        off[q + 1] = off[q] + cnt;
+    }
+}
+
+// What the host-only plan calls check before they read the structure.
+static int halo_args(int64_t n, int S, const int64_t *row_ptr, const int32_t *col_idx, const char *what) {
+    if (n < 1) return fail(CGX_ERR_ARG, "%s: n must be >= 1 (got %lld)", what, (long long)n);
+    if (S < 1 || S > kMaxShards) return fail(CGX_ERR_ARG, "%s: nshards must be in [1, %d] (got %d)", what, kMaxShards, S);
+    if (!row_ptr) return fail(CGX_ERR_ARG, "%s: row_ptr is NULL", what);
+    if (n % S != 0)
+        return fail(CGX_ERR_SHAPE, "%s: %lld rows are not divisible by %d row blocks", what, (long long)n, S);
+    const int64_t nnz = row_ptr[n];
+    if (nnz < 0) return fail(CGX_ERR_SHAPE, "%s: row_ptr[n] = %lld is negative", what, (long long)nnz);
+    return cgx_csr_check(n, nnz, row_ptr, col_idx);
 }
 
 // The block kind's W goes (z stays with the context: free_shard); the stream is idle.
@@ -74,6 +130,8 @@ static int pc_need_ctx(const cgx_ctx *c, const char *what) {
     if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "%s: not a cgx_create_csr context", what);
     // OP_CSR alone does not do: the K-column update kernels have no PCG form
     if (c->nr) return fail(CGX_ERR_ARG, "%s: not with several right-hand sides (a cgx_create_csr_nrhs context)", what);
+    // the PCG kernels read their scalars from one block's slots
+    if (c->csr_multi) return fail(CGX_ERR_ARG, "%s: not over row blocks (a cgx_create_csr_multi context)", what);
     return CGX_OK;
 }
 // ... and that it has a matrix.
@@ -177,6 +235,107 @@ static int pc_block_install(cgx_ctx *c, int bs, const double *W) {
     return CGX_OK;
 }
 
+// The matrix of a cgx_create_csr_multi context, after csr_upload's checks: block
+// i gets its rows' row_ptr rebased to 0, its slices of col_idx (still global
+// columns) and of the values, and its exchange lists (halo_block).  Whatever
+// can refuse the call -- a block above its room, a host or a device allocation
+// -- comes before the first byte moves: a refused call leaves the earlier
+// matrix, its value type and its lists.
+static int csr_upload_blocks(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, const void *values, bool f32,
+                             const char *what) {
+    const int S = (int)c->sh.size();
+    const int64_t n = c->n, nloc = n / S, nnz = row_ptr[n];
+    for (int i = 0; i < S; ++i) {
+        const int64_t cnt = row_ptr[(i + 1) * nloc] - row_ptr[i * nloc];
+        if (cnt > c->csr_cap)
+            return fail(CGX_ERR_SHAPE, "%s: row block %d (rows %lld .. %lld) has %lld entries, every block has room "
+                                       "for %lld", what, i, (long long)(i * nloc), (long long)((i + 1) * nloc - 1),
+                        (long long)cnt, (long long)c->csr_cap);
+    }
+    std::vector<std::vector<int32_t>> lists((size_t)S);
+    std::vector<GatherLists> offs((size_t)S, GatherLists{});
+    std::vector<int64_t> counts((size_t)S * S, 0), rp;
+    try {
+        std::vector<uint8_t> mark((size_t)n, 0);
+        rp.resize((size_t)nloc + 1);
+        for (int d = 0; d < S; ++d) {
+            halo_block(n, S, row_ptr, col_idx, d, mark, offs[d].off, &lists[d]);
+            for (int q = 0; q < S; ++q) counts[(size_t)d * S + q] = offs[d].off[q + 1] - offs[d].off[q];
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    TRY(sync_all(c));  // iterations still enqueued read the arrays and the lists
+    std::vector<char *> fresh((size_t)S, nullptr);  // list buffers that have to grow
+    auto drop_fresh = [&] {
+        for (int i = 0; i < S; ++i)
+            if (fresh[i] && hipSetDevice(c->sh[i].dev) == hipSuccess) (void)hipFree(fresh[i]);
+    };
+    for (int i = 0; i < S; ++i) {
+        const Shard &s = c->sh[i];
+        const size_t need = lists[i].size();
+        if ((int64_t)need <= s.halo_cap) continue;
+        hipError_t e = hipSetDevice(s.dev);
+        if (e == hipSuccess) e = hipMalloc(&fresh[i], need * 4);
+        if (e != hipSuccess) {
+            fresh[i] = nullptr;
+            drop_fresh();
+            return fail(CGX_ERR_NOMEM, "hipMalloc(%zu bytes) on device %d: %s", need * 4, s.dev, hipGetErrorString(e));
+        }
+    }
+    const size_t vb = f32 ? 4 : 8;
+    const int rc = [&]() -> int {
+        for (int i = 0; i < S; ++i) {
+            Shard &s = c->sh[i];
+            TRY(set_dev(s));
+            const int64_t e0 = row_ptr[i * nloc], cnt = row_ptr[(i + 1) * nloc] - e0;
+            for (int64_t j = 0; j <= nloc; ++j) rp[j] = row_ptr[i * nloc + j] - e0;
+            HIPT(hipMemcpyAsync(s.csr_rp, rp.data(), (size_t)(nloc + 1) * 8, hipMemcpyHostToDevice, s.stream));
+            if (cnt > 0) {
+                HIPT(hipMemcpyAsync(s.csr_ci, col_idx + e0, (size_t)cnt * 4, hipMemcpyHostToDevice, s.stream));
+                HIPT(hipMemcpyAsync(s.csr_val, static_cast<const char *>(values) + (size_t)e0 * vb, (size_t)cnt * vb,
+                                    hipMemcpyHostToDevice, s.stream));
+            }
+            if (!lists[i].empty())
+                HIPT(hipMemcpyAsync(fresh[i] ? fresh[i] : s.halo_idx, lists[i].data(), lists[i].size() * 4,
+                                    hipMemcpyHostToDevice, s.stream));
+            HIPT(hipStreamSynchronize(s.stream));  // rp is the next block's staging too
+        }
+        return CGX_OK;
+    }();
+    if (rc != CGX_OK) {  // some blocks hold the new rows, some the old: no matrix until the next cgx_set_csr
+        drop_fresh();
+        c->csr_nnz = -1;
+        c->state = ST_IDLE;
+        return rc;
+    }
+    for (int i = 0; i < S; ++i) {
+        Shard &s = c->sh[i];
+        if (fresh[i]) {
+            TRY(set_dev(s));
+            if (s.halo_idx) HIPT(hipFree(s.halo_idx));
+            s.halo_idx = fresh[i];
+            s.halo_cap = (int64_t)lists[i].size();
+        }
+        s.halo = offs[i];
+    }
+    c->halo_counts = counts;
+    c->csr_nnz = nnz;
+    c->csr_f32 = f32;
+    if (!c->csr_plan_user) {
+        // one T for the context, the one a cgx_create_csr context chooses for this matrix (n, nnz);
+        // each block's grid from its own rows
+        TRY(set_dev(c->sh[0]));
+        const MatvecPlan whole = plan_spmv_csr(c->sh[0].dev, n, nnz, 0, -1, 0, f32);
+        for (auto &s : c->sh) {
+            TRY(set_dev(s));
+            s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 64 / whole.R, whole.nt, 0, f32);
+        }
+    }
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
 // cgx_set_csr (f32 = false: values is double[nnz]) and cgx_set_csr_f32 (float[nnz]):
 // the same checks in the same order, then the upload.  Float values take the
 // first 4 nnz bytes of the value buffer and stay float there; the context's
@@ -188,11 +347,12 @@ static int csr_upload(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx
     if (!row_ptr) return fail(CGX_ERR_ARG, "%s: row_ptr is NULL", what);
     const int64_t nnz = row_ptr[c->n];  // the entry count a valid row_ptr states; the check below tests the rest
     if (nnz < 0) return fail(CGX_ERR_SHAPE, "%s: row_ptr[n] = %lld is negative", what, (long long)nnz);
-    if (nnz > c->csr_cap)
+    if (nnz > c->csr_cap && !c->csr_multi)  // row blocks: the room is per block, checked once the structure stands
         return fail(CGX_ERR_SHAPE, "%s: %lld entries, the context has room for %lld", what, (long long)nnz,
                     (long long)c->csr_cap);
     if (nnz > 0 && (!col_idx || !values)) return fail(CGX_ERR_ARG, "%s: col_idx / values is NULL", what);
     TRY(cgx_csr_check(c->n, nnz, row_ptr, col_idx));  // nothing is uploaded when it fails
+    if (c->csr_multi) return csr_upload_blocks(c, row_ptr, col_idx, values, f32, what);
     Shard &s = c->sh[0];
     TRY(sync_all(c));  // iterations still enqueued read the arrays
     TRY(set_dev(s));
@@ -400,6 +560,64 @@ int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t 
         if (col_idx[e] < 0 || (int64_t)col_idx[e] >= n)
             return fail(CGX_ERR_SHAPE, "cgx_csr_check: col_idx[%lld] = %d outside [0, %lld)", (long long)e,
                         (int)col_idx[e], (long long)n);
+    return CGX_OK;
+}
+
+int cgx_csr_halo_counts(int64_t n, int nshards, const int64_t *row_ptr, const int32_t *col_idx, int64_t *counts) {
+    if (!counts) return fail(CGX_ERR_ARG, "cgx_csr_halo_counts: counts is NULL");
+    TRY(halo_args(n, nshards, row_ptr, col_idx, "cgx_csr_halo_counts"));
+    try {
+        std::vector<uint8_t> mark((size_t)n, 0);
+        int64_t off[kMaxShards + 1];
+        for (int d = 0; d < nshards; ++d) {
+            halo_block(n, nshards, row_ptr, col_idx, d, mark, off, nullptr);
+            for (int q = 0; q < nshards; ++q) counts[(size_t)d * nshards + q] = off[q + 1] - off[q];
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    return CGX_OK;
+}
+
+int cgx_csr_halo_list(int64_t n, int nshards, const int64_t *row_ptr, const int32_t *col_idx, int dst, int src,
+                      int32_t *offsets) {
+    TRY(halo_args(n, nshards, row_ptr, col_idx, "cgx_csr_halo_list"));
+    if (dst < 0 || dst >= nshards || src < 0 || src >= nshards)
+        return fail(CGX_ERR_ARG, "cgx_csr_halo_list: blocks (%d, %d) outside [0, %d)", dst, src, nshards);
+    try {
+        std::vector<uint8_t> mark((size_t)n, 0);
+        std::vector<int32_t> lists;
+        int64_t off[kMaxShards + 1];
+        halo_block(n, nshards, row_ptr, col_idx, dst, mark, off, &lists);
+        if (off[src + 1] > off[src]) {
+            if (!offsets) return fail(CGX_ERR_ARG, "cgx_csr_halo_list: offsets is NULL");
+            std::memcpy(offsets, lists.data() + off[src], (size_t)(off[src + 1] - off[src]) * 4);
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(CGX_ERR_NOMEM, "host allocation failed");
+    }
+    return CGX_OK;
+}
+
+int cgx_get_csr_halo(cgx_ctx *c, int64_t *counts) {
+    if (!c || !counts) return fail(CGX_ERR_ARG, "cgx_get_csr_halo: NULL argument");
+    if (!c->csr_multi) return fail(CGX_ERR_ARG, "cgx_get_csr_halo: not a cgx_create_csr_multi context");
+    TRY(csr_need_matrix(c, "cgx_get_csr_halo"));
+    std::memcpy(counts, c->halo_counts.data(), c->halo_counts.size() * 8);
+    return CGX_OK;
+}
+
+int cgx_gather_indexed(const void *src, const void *idx, int64_t count, void *dst, void *stream) {
+    if (count < 0) return fail(CGX_ERR_SHAPE, "cgx_gather_indexed: bad count");
+    if (count == 0) return CGX_OK;
+    if (!src || !idx || !dst) return fail(CGX_ERR_ARG, "cgx_gather_indexed: NULL pointer");
+    PeerTable t{};
+    t.p[0] = static_cast<const char *>(src);
+    GatherLists one{};
+    one.off[1] = count;
+    // one source, never the whole-slice form (nloc = -1): every entry goes through its index
+    HIPT(gather_indexed(t, 1, -1, -1, one, static_cast<const int32_t *>(idx), -1, static_cast<double *>(dst),
+                        static_cast<hipStream_t>(stream)));
     return CGX_OK;
 }
 

@@ -4,7 +4,7 @@
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
 //   cgx_nrhs.hip      cgx_create_nrhs / cgx_create_csr_nrhs contexts: several systems per pass over A
-//   cgx_csr.hip       cgx_create_csr contexts: A in CSR storage (structure check, upload), diagonal and block preconditioning
+//   cgx_csr.hip       cgx_create_csr / cgx_create_csr_multi contexts: A in CSR storage (structure check, upload, the row blocks' exchange lists), diagonal and block preconditioning
 //   cgx_pcblock.hip   block Jacobi's host side: the blocks' Cholesky inversion and the check of a caller's blocks
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
@@ -190,6 +190,12 @@ struct Shard {
     // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap], or the
     // first half of it as float[csr_cap] while cgx_ctx::csr_f32); no s.A
     char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
+    // cgx_create_csr_multi: this block's rows only (row_ptr rebased to 0, col_idx still global), and its exchange
+    // lists -- for every other block q the ascending offsets into q's slice that this block's col_idx names, source
+    // after source in halo_idx (int32[halo_cap]), list q at halo.off[q] .. halo.off[q + 1]
+    char *halo_idx = nullptr;
+    int64_t halo_cap = 0;
+    GatherLists halo{};
     char *pc_minv = nullptr;  // ... and the preconditioner's n values (cgx_ctx::pc_kind JACOBI or DIAG)
     // CGX_PC_BLOCK: the inverse blocks, entry (i, j) of block k at pc_w[(i * bs + j) * pc_wld + k], and z = W r
     // (n doubles, allocated when the kind is first set, kept until the context goes)
@@ -297,6 +303,11 @@ struct cgx_ctx {
     int64_t csr_cap = 0, csr_nnz = -1;
     bool csr_plan_user = false;
     bool csr_f32 = false;
+    // cgx_create_csr_multi (whatever the block count): csr_cap is every block's room; halo_counts[d * S + q] =
+    // the length of block d's list into block q (cgx_get_csr_halo); csr_halo: several blocks exchange p and x
+    // through those lists (gather_indexed; false: whole slices, CGX_CSR_XCHG=full or CGX_LOCAL_XCHG=copy)
+    bool csr_multi = false, csr_halo = false;
+    std::vector<int64_t> halo_counts;
     // cgx_set_precond / cgx_set_precond_diag: CGX_PC_NONE, or the iteration runs the PCG kernels on
     // sh[0].pc_minv (cgx_pcg.hip); cgx_set_csr goes back to CGX_PC_NONE
     int pc_kind = CGX_PC_NONE;
@@ -406,6 +417,8 @@ inline bool f32ref(const cgx_ctx *c) { return (c->flags & CGX_F32_REF) != 0; }
 inline bool a32(const cgx_ctx *c) { return (c->flags & CGX_A_F32) != 0; }
 // a cgx_create_csr context's values with their type (double, or float after cgx_set_csr_f32)
 inline CsrValues csr_values(const cgx_ctx *c) { return CsrValues(c->sh[0].csr_val, c->csr_f32); }
+// ... and row block s's (cgx_create_csr_multi; the one block of any other CSR context)
+inline CsrValues csr_values(const cgx_ctx *c, const Shard &s) { return CsrValues(s.csr_val, c->csr_f32); }
 inline void *slot(const Shard &s, int i) { return s.scal + 8 * i; }
 inline bool p2p(const cgx_ctx *c) { return (c->flags & CGX_COMM_P2P) != 0; }
 // Where a kernel writes its (partial) scalar: the global slot directly when
@@ -465,6 +478,7 @@ int exchange_halo_of(cgx_ctx *c, char *Shard::*slab);
 int p2p_allgather(cgx_ctx *c, bool from_x);
 int p2p_scalar(cgx_ctx *c, int lslot, int gslot);
 int exchange_allgather(cgx_ctx *c, bool from_x);
+int gather_block(const cgx_ctx *c, const Shard &d, bool from_x, hipStream_t st);
 int exchange_scalar(cgx_ctx *c, int lslot, int gslot);
 PeerSum peer_sum(const cgx_ctx *c, const Shard &d, int lslot, int gslot);
 PeerSumF32 peer_sum_f32(const cgx_ctx *c, const Shard &d, int lslot, int gslot);

@@ -386,6 +386,22 @@ int p2p_scalar(cgx_ctx *c, int lslot, int gslot) {
     return local_barrier(c);  // as in p2p_allgather: shard 0's slots stay put until copied
 }
 
+// Row block d's pull of the other blocks' p (from_x: of every block's x, its
+// own included) on stream st, which has waited for the producers: one launch.
+// A sparse A's blocks (c->csr_halo) pull only the entries their col_idx names
+// (the lists cgx_set_csr built: gather_indexed); their pfull is never written,
+// and never read, anywhere else outside the own slice.
+int gather_block(const cgx_ctx *c, const Shard &d, bool from_x, hipStream_t st) {
+    const PeerTable src = peer_table(c, from_x ? &Shard::x : &Shard::pown, 0);
+    const int S = (int)c->sh.size();
+    if (c->csr_halo)
+        HIPT(gather_indexed(src, S, from_x ? -1 : d.index, from_x ? d.index : -1, d.halo,
+                            reinterpret_cast<const int32_t *>(d.halo_idx), d.nloc, f64(d.pfull), st));
+    else
+        HIPT(gather_slices(src, S, from_x ? -1 : d.index, d.nloc * (int64_t)c->es, d.pfull, st));
+    return CGX_OK;
+}
+
 // Every shard's pfull gets every shard's slice of `src(shard)` (its own slice
 // of a full-length buffer when in_place, else a separate local buffer).
 int exchange_allgather(cgx_ctx *c, bool from_x) {
@@ -414,11 +430,9 @@ int exchange_allgather(cgx_ctx *c, bool from_x) {
     // copy per pair).
     TRY(local_barrier(c));
     if (c->xchg_kernels) {
-        const PeerTable src = peer_table(c, from_x ? &Shard::x : &Shard::pown, 0);
         for (auto &d : c->sh) {
             TRY(set_dev(d));
-            HIPT(gather_slices(src, (int)c->sh.size(), from_x ? -1 : d.index, d.nloc * (int64_t)es, d.pfull,
-                               d.stream));
+            TRY(gather_block(c, d, from_x, d.stream));
         }
         return CGX_OK;
     }

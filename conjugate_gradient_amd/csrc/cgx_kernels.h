@@ -33,6 +33,17 @@ struct PeerTable {
 // copies every slice): the allgather of p (or of x) in one launch instead of
 // cnt - 1 peer copies.
 hipError_t gather_slices(const PeerTable &src, int cnt, int skip, int64_t slice_bytes, char *dst, hipStream_t s);
+// The indexed form of gather_slices for a sparse A's row blocks (cgx_create_csr_multi): of source q's slice of
+// nloc doubles only the entries its list names, dst[q * nloc + j] = src.p[q][j] for the j in
+// idx[lists.off[q] .. lists.off[q + 1]) (offsets into the slice, each once).  A source whose list has nloc
+// entries, and source `whole` (the consumer's own x; < 0: none), is the contiguous slice, no index reads;
+// source `skip` (< 0: none) and an empty list move nothing.  The offsets are not range-checked: the host
+// builds them from a checked structure (cgx_csr.hip).
+struct GatherLists {
+    int64_t off[kMaxPeers + 1];
+};
+hipError_t gather_indexed(const PeerTable &src, int cnt, int skip, int whole, const GatherLists &lists,
+                          const int32_t *idx, int64_t nloc, double *dst, hipStream_t s);
 // *out = the cnt partials src.p[q] (fp64), summed in q order: the rank-order
 // combine of exchange_scalar read straight from each shard's slot.
 hipError_t combine_peers_f64(const PeerTable &src, int cnt, double *out, hipStream_t s);

@@ -14,7 +14,8 @@
 // reuse safe: a block re-records an event only after passing two more
 // barriers, by which time every other block has enqueued its wait on it.
 //
-// Used for the dense fp64 iteration with the folded scalar combines, gated
+// Used for the dense fp64 iteration (and a sparse A's row blocks,
+// cgx_create_csr_multi) with the folded scalar combines, gated
 // or fixed-count (the host-checked form reads r.r between the kernels and
 // stays on the single-thread path), when the blocks span distinct devices
 // (local_mt_eligible).
@@ -93,6 +94,11 @@ static int shard_iteration(LocalPool &P, Shard &d) {
         for (auto &s : c->sh) HIPT(hipStreamWaitEvent(d.cstream, s.ev_pready, 0));
         HIPT(gather_slices(pown, S, d.index, d.nloc * (int64_t)es, d.pfull, d.cstream));
         TRY(overlap_matvecs(c, d, pl, gated));
+    } else if (c->op == OP_CSR) {  // a sparse A's row block: its pull of p (indexed or whole slices), then its SpMV
+        for (auto &s : c->sh)
+            if (&s != &d) HIPT(hipStreamWaitEvent(d.stream, s.ev_pready, 0));
+        TRY(gather_block(c, d, false, d.stream));
+        TRY(launch_matvec(c, d, d.pfull, true, pl, gated));
     } else {  // MPI_Allgather(local_p -> p), then the matVec (parallel_cg.c:290-293)
         TRY(timing_begin(c, d));
         for (auto &s : c->sh)
@@ -159,7 +165,7 @@ static void worker(LocalPool *P, int index) {
 bool local_mt_eligible(const cgx_ctx *c) {
     const char *e = std::getenv("CGX_LOCAL_THREADS");
     if (!(e && *e == '1')) return false;
-    return c->mode == M_LOCAL && c->fuse_combine && c->op == OP_DENSE && !f32ref(c) &&
+    return c->mode == M_LOCAL && c->fuse_combine && (c->op == OP_DENSE || c->op == OP_CSR) && !f32ref(c) &&
            !(c->flags & (CGX_HOST_STREAM | CGX_SYMMETRIC | CGX_COMM_P2P)) && c->sh.size() >= 2;
 }
 

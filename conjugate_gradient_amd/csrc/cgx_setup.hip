@@ -232,7 +232,7 @@ void free_shard(Shard &s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm) ncclCommDestroy(s.comm);
     for (char *p : {s.A, s.b, s.x, s.rh ? s.rh : s.r, s.p2, s.p3, s.Ap, s.pfull, s.p_alt, s.xfull, s.scal, s.sym_prow,
-                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.pc_minv, s.pc_w, s.pc_z})
+                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.halo_idx, s.pc_minv, s.pc_w, s.pc_z})
         if (p) (void)hipFree(p);
     if (s.ws.partials) (void)hipFree(s.ws.partials);
     if (s.ws.tickets) (void)hipFree(s.ws.tickets);
@@ -380,6 +380,10 @@ int finish_create(cgx_ctx *c, cgx_ctx **out) {
         c->fuse_f32 = c->mode == M_LOCAL && c->xchg_kernels && !(f && *f == '0') && (c->flags & CGX_F32_REF) &&
                       !(c->flags & CGX_COMM_P2P) && (int)c->sh.size() <= kMaxPeers && c->op == OP_DENSE;
     }
+    {  // a sparse A's row blocks pull only the entries of p their columns name (CGX_CSR_XCHG=full: whole slices)
+        const char *e = std::getenv("CGX_CSR_XCHG");
+        c->csr_halo = c->csr_multi && c->mode == M_LOCAL && c->xchg_kernels && !(e && !std::strcmp(e, "full"));
+    }
     c->rot = can_rotate(c);
     c->overlap = false;  // choose_overlap below, once the row blocks exist
     c->fused_p = can_fuse_p(c);
@@ -507,7 +511,9 @@ static int create_single(cgx_ctx **ctx, int op, int64_t n, int64_t m, int device
     return finish_create(c, ctx);
 }
 
-static int create_multi(cgx_ctx **ctx, int op, int64_t n, int64_t m, int nshards, const int *devices, int flags) {
+// csr_cap: every block's room for entries (cgx_create_csr_multi, which has checked its own arguments)
+static int create_multi(cgx_ctx **ctx, int op, int64_t n, int64_t m, int nshards, const int *devices, int flags,
+                        int64_t csr_cap = 0) {
     if (!ctx || !devices) return fail(CGX_ERR_ARG, "ctx/devices is NULL");
     *ctx = nullptr;
     if (nshards < 1 || nshards > kMaxShards) return fail(CGX_ERR_ARG, "nshards must be in [1, %d]", kMaxShards);
@@ -516,6 +522,8 @@ static int create_multi(cgx_ctx **ctx, int op, int64_t n, int64_t m, int nshards
     cgx_ctx *c = new_ctx_op(op, n, m, nshards, flags);
     if (!c) return fail(CGX_ERR_NOMEM, "host allocation failed");
     c->mode = nshards == 1 ? M_SINGLE : M_LOCAL;
+    c->csr_multi = op == OP_CSR;
+    c->csr_cap = csr_cap;
     c->sh.resize(nshards);
     const int64_t loc = n / nshards;
     for (int i = 0; i < nshards; ++i) {
@@ -714,6 +722,30 @@ int cgx_create_csr(cgx_ctx **ctx, int64_t n, int64_t nnz, int device, int flags)
     return finish_create(c, ctx);
 }
 
+// A sparse A over nshards row blocks in this process (cgx_csr.hip): a
+// cgx_create_multi context whose blocks each own the CSR arrays of their rows,
+// with room for nnz_block entries, instead of their rows of a dense A.  The
+// arguments are checked before any device is touched.
+int cgx_create_csr_multi(cgx_ctx **ctx, int64_t n, int64_t nnz_block, int nshards, const int *devices, int flags) {
+    if (!ctx) return fail(CGX_ERR_ARG, "cgx_create_csr_multi: ctx is NULL");
+    *ctx = nullptr;
+    if (!devices) return fail(CGX_ERR_ARG, "cgx_create_csr_multi: devices is NULL");
+    if (nshards < 1 || nshards > kMaxShards)
+        return fail(CGX_ERR_ARG, "cgx_create_csr_multi: nshards must be in [1, %d] (got %d)", kMaxShards, nshards);
+    if (n < 1) return fail(CGX_ERR_ARG, "cgx_create_csr_multi: n must be >= 1 (got %lld)", (long long)n);
+    if (n > (int64_t)INT32_MAX)
+        return fail(CGX_ERR_ARG, "cgx_create_csr_multi: n must be below 2^31, col_idx is int32 (got %lld)",
+                    (long long)n);
+    if (nnz_block < 0)
+        return fail(CGX_ERR_ARG, "cgx_create_csr_multi: nnz_block must be >= 0 (got %lld)", (long long)nnz_block);
+    if (flags & ~CGX_TIMING)
+        return fail(CGX_ERR_ARG, "cgx_create_csr_multi: CGX_F64 (optionally with CGX_TIMING) only (flags 0x%x)", flags);
+    if (n % nshards != 0)
+        return fail(CGX_ERR_SHAPE, "cgx_create_csr_multi: %lld rows are not divisible by %d row blocks", (long long)n,
+                    nshards);
+    return create_multi(ctx, OP_CSR, n, 0, nshards, devices, flags, nnz_block);
+}
+
 // nrhs systems on one CSR matrix (cgx_nrhs.hip, cgx_spmm.hip): a cgx_create_csr
 // context whose vectors, scalars and iteration are a cgx_create_nrhs
 // context's.  The arguments are checked before any device is touched.
@@ -833,7 +865,8 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
                   (c->pool ? CGX_THREADS_ACTIVE : 0) | (c->halo_overlap ? CGX_HALO_OVERLAP_ACTIVE : 0);
     if (c->op == OP_CSR)
         info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0) |
-                       (c->csr_f32 ? CGX_A_F32 : 0);  // float-valued since cgx_set_csr_f32
+                       (c->csr_f32 ? CGX_A_F32 : 0) |  // float-valued since cgx_set_csr_f32
+                       (c->csr_halo ? CGX_CSR_HALO_ACTIVE : 0);
     info->elem_bytes = c->es;
     return CGX_OK;
 }

@@ -532,7 +532,62 @@ __global__ __launch_bounds__(kNT) void k_gather_slices(PeerTable src, int skip, 
     }
 }
 
+// The same pull for a sparse A's row blocks (GatherLists, cgx_kernels.h): blockIdx.y = the source block q, of whose
+// slice only the listed entries move -- a thread reads kGU offsets, issues its kGU system-scope loads of
+// src.p[q][offset], then stores them at the same offsets of dst's slice q.  A list that names the whole slice (a dense
+// row or column; or the consumer's own x) takes the offsets from the loop counter: k_gather_slices' loads and stores.
+// An entry past the end repeats the last one's loads (a valid address: words >= 1 inside the loop) and is not stored,
+// so no branch sits between the loads: the kGU offset reads go out together, then the kGU value reads, then the stores.
+template <bool ALL>
+__device__ __forceinline__ void gather_listed(const uint64_t *__restrict__ in, const int32_t *__restrict__ ix,
+                                              int64_t words, uint64_t *__restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * kNT * kGU;
+    for (int64_t base = (int64_t)blockIdx.x * kNT * kGU + threadIdx.x; base < words; base += stride) {
+        int64_t j[kGU];
+        uint64_t v[kGU];
+#pragma unroll
+        for (int u = 0; u < kGU; ++u) {
+            const int64_t e = min(base + u * kNT, words - 1);
+            j[u] = ALL ? e : (int64_t)ix[e];
+        }
+#pragma unroll
+        for (int u = 0; u < kGU; ++u) v[u] = load_sys(in + j[u]);
+#pragma unroll
+        for (int u = 0; u < kGU; ++u)
+            if (base + u * kNT < words) out[j[u]] = v[u];
+    }
+}
+
+__global__ __launch_bounds__(kNT) void k_gather_indexed(PeerTable src, GatherLists lists, int skip, int whole,
+                                                        const int32_t *__restrict__ idx, int64_t nloc,
+                                                        uint64_t *__restrict__ dst) {
+    const int q = blockIdx.y;
+    if (q == skip) return;
+    const int64_t first = lists.off[q], cnt = lists.off[q + 1] - first;
+    const uint64_t *__restrict__ in = reinterpret_cast<const uint64_t *>(src.p[q]);
+    uint64_t *__restrict__ out = dst + (int64_t)q * (nloc > 0 ? nloc : 0);
+    if (q == whole || cnt == nloc) gather_listed<true>(in, nullptr, nloc, out);
+    else gather_listed<false>(in, idx + first, cnt, out);
+}
+
 }  // namespace
+
+hipError_t gather_indexed(const PeerTable &src, int cnt, int skip, int whole, const GatherLists &lists,
+                          const int32_t *idx, int64_t nloc, double *dst, hipStream_t s) {
+    if (cnt < 1 || cnt > kMaxPeers || (reinterpret_cast<uintptr_t>(dst) % 8) != 0) return hipErrorInvalidValue;
+    int64_t most = 0;  // the longest move of any source: the grid's width
+    for (int q = 0; q < cnt; ++q) {
+        const int64_t c = lists.off[q + 1] - lists.off[q];
+        if (c < 0 || (reinterpret_cast<uintptr_t>(src.p[q]) % 8) != 0) return hipErrorInvalidValue;
+        if (q != skip) most = std::max(most, q == whole ? nloc : c);
+    }
+    if (most == 0) return hipSuccess;
+    const int64_t per_block = (int64_t)kNT * kGU;
+    const unsigned gx = (unsigned)std::min<int64_t>((most + per_block - 1) / per_block, 64);
+    hipLaunchKernelGGL(k_gather_indexed, dim3(gx, (unsigned)cnt), dim3(kNT), 0, s, src, lists, skip, whole, idx, nloc,
+                       reinterpret_cast<uint64_t *>(dst));
+    return hipGetLastError();
+}
 
 hipError_t gather_slices(const PeerTable &src, int cnt, int skip, int64_t slice_bytes, char *dst, hipStream_t s) {
     if (cnt < 1 || cnt > kMaxPeers || slice_bytes < 0 || (slice_bytes & 3)) return hipErrorInvalidValue;

@@ -265,6 +265,66 @@
  *       4 bytes per entry is not built.
  *     - Kernel-level: cgx_spmv_csr_f32, cgx_spmm_csr_f32.  cgx_csr_diag_blocks
  *       takes double values only.
+ *   - Several row blocks (cgx_create_csr_multi): one process, nshards
+ *     contiguous equal row blocks of n / nshards rows on devices[0 ..
+ *     nshards - 1] (a device may repeat), as cgx_create_multi makes them; each
+ *     block owns the CSR arrays of its rows with room for nnz_block entries.
+ *     - Refused before any device is touched (*ctx NULL): n % nshards != 0
+ *       (CGX_ERR_SHAPE); nshards outside [1, 32], n < 1, n >= 2^31,
+ *       nnz_block < 0, any flag bit but CGX_TIMING, a NULL pointer
+ *       (CGX_ERR_ARG).
+ *     - cgx_set_csr / cgx_set_csr_f32 take the whole matrix's host arrays
+ *       (row_ptr[n + 1], global col_idx, values) and run the checks above in
+ *       the same order (the room is per block, so the total is not compared
+ *       with it); then a block with more than nnz_block entries is
+ *       CGX_ERR_SHAPE naming the block and its count.  Nothing is uploaded
+ *       and no list is replaced when a check fails: the earlier matrix, its
+ *       value type and its lists stay, and a later solve gives the bits it
+ *       gave before.  Block i receives its rows' row_ptr rebased to start at
+ *       0 and its slices of col_idx (still global columns) and values.  The
+ *       call ends a solve in progress.
+ *     - One T for the context: by default the T plan_spmv_csr chooses for
+ *       the whole matrix (n, all its entries), which is what a cgx_create_csr
+ *       context chooses; each block's grid comes from its own rows.
+ *       cgx_set_matvec_plan applies to every block under the rules above.
+ *     - The exchange.  A block needs only the entries of p that its col_idx
+ *       names outside its own rows.  cgx_set_csr builds, on the host, for
+ *       every pair (d, q != d) the ascending distinct offsets into block q
+ *       that block d's rows name (one pass over the block's col_idx with a
+ *       mark array, then a scan; cgx_csr_halo_counts / cgx_csr_halo_list run
+ *       the same builder without a GPU), and one pull kernel per consuming
+ *       block (k_gather_indexed, after the producers' events) moves exactly
+ *       those entries into the block's full-length p each iteration; the
+ *       same lists serve the exchange of x at the start of a solve from
+ *       x0 != 0 and in cgx_residual_norm.  A pair whose list is the whole
+ *       slice (a dense row or column) takes the contiguous path, an empty
+ *       list moves nothing.  Positions of the full-length p outside the own
+ *       slice and the lists are never written, and no kernel reads them.
+ *       CGX_CSR_XCHG=full runs the whole-slice pull kernel of
+ *       cgx_create_multi instead, CGX_LOCAL_XCHG=copy its peer copies; the
+ *       three forms give the same x bit for bit, and cgx_get_info carries
+ *       CGX_CSR_HALO_ACTIVE only under the first.
+ *     - Memory: the full-length p costs n doubles on every block (134 MB per
+ *       block at 16.8 M rows), whatever the lists' lengths.
+ *     - Bits: given the same p, a block's rows of A p are the one-GPU
+ *       kernel's row sums bit for bit at the same T, float-stored values
+ *       included; p.Ap and r.r are each block's fixed-order partial sums
+ *       combined in block order.  So x agrees with a one-GPU solve to fp64
+ *       rounding and is deterministic for a partition and a plan: the same
+ *       bits in every host form (device-gated, CGX_GATED=0, fixed count, in
+ *       pieces), under every exchange form, with CGX_LOCAL_FUSE=0 / 1 and
+ *       CGX_LOCAL_THREADS=0 / 1, on distinct devices as on one device
+ *       repeated.  With nshards == 1 the context gives cgx_create_csr's x,
+ *       loop count and r.r bit for bit.
+ *     - The iteration stays the three-launch one (no two-launch forms, no
+ *       creation warm-up); the dense overlap does not apply
+ *       (cgx_get_overlap_info: CGX_OV_NA).
+ *     - Refused (CGX_ERR_ARG) whatever nshards is: cgx_set_precond,
+ *       cgx_set_precond_diag, cgx_set_precond_block[_values] (the PCG kernels
+ *       read their scalars from one block's slots), cgx_generate_spd, a
+ *       non-NULL A.  cgx_solve_begin, cgx_solve, cgx_residual_norm and
+ *       cgx_get_csr_halo before the first cgx_set_csr: CGX_ERR_STATE.
+ *       cgx_create_csr_nrhs stays one GPU.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -294,7 +354,10 @@ extern "C" {
                            likewise cgx_set_precond_block and its entry points and the kind
                            CGX_PC_BLOCK (new functions only, no new bit); likewise
                            cgx_set_csr_f32, cgx_spmv_csr_f32 and cgx_spmm_csr_f32 (new functions
-                           only; CGX_A_F32 is also reported by a float-valued CSR context) */
+                           only; CGX_A_F32 is also reported by a float-valued CSR context); likewise
+                           cgx_create_csr_multi, cgx_csr_halo_counts, cgx_csr_halo_list,
+                           cgx_get_csr_halo and cgx_gather_indexed, and the reported bit
+                           CGX_CSR_HALO_ACTIVE */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -414,6 +477,9 @@ extern "C" {
 #define CGX_CSR_ACTIVE 0x8000000   /* reported in cgx_info.flags: a cgx_create_csr context */
 #define CGX_PRECOND_ACTIVE 0x10000000 /* reported in cgx_info.flags: a cgx_create_csr context iterating
                                          with a diagonal preconditioner (cgx_set_precond) */
+#define CGX_CSR_HALO_ACTIVE 0x20000000 /* reported in cgx_info.flags: a cgx_create_csr_multi context whose
+                                         row blocks exchange p by index lists (k_gather_indexed; else whole
+                                         slices: CGX_CSR_XCHG=full, CGX_LOCAL_XCHG=copy, or one block) */
 
 typedef struct cgx_ctx cgx_ctx;
 
@@ -629,6 +695,24 @@ int cgx_set_csr_f32(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx
  * nnz entries, solved together, one read of the CSR arrays per iteration.
  * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
 int cgx_create_csr_nrhs(cgx_ctx **ctx, int64_t n, int64_t nnz, int nrhs, int device, int flags);
+/* One process, nshards row blocks of n / nshards rows on devices[0..nshards-1] (a device may
+ * repeat), A as CSR, fp64.  nnz_block: room for that many entries in every row block.
+ * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
+int cgx_create_csr_multi(cgx_ctx **ctx, int64_t n, int64_t nnz_block, int nshards,
+                         const int *devices, int flags);
+/* Host-only, no GPU: the exchange plan of a matrix over nshards equal row blocks.
+ * counts[d * nshards + q] = how many distinct columns of block q's row range occur in block d's
+ * rows (0 on the diagonal d == q).  The structure must pass cgx_csr_check (run first;
+ * CGX_ERR_SHAPE as there); n % nshards != 0 is CGX_ERR_SHAPE. */
+int cgx_csr_halo_counts(int64_t n, int nshards, const int64_t *row_ptr, const int32_t *col_idx,
+                        int64_t *counts);
+/* The list of one pair: counts[dst * nshards + src] offsets into block src (column - src's first
+ * row), ascending, each once. */
+int cgx_csr_halo_list(int64_t n, int nshards, const int64_t *row_ptr, const int32_t *col_idx,
+                      int dst, int src, int32_t *offsets);
+/* The counts in use on a live context (nshards * nshards entries); CGX_ERR_STATE before the first
+ * cgx_set_csr, CGX_ERR_ARG on any other kind of context. */
+int cgx_get_csr_halo(cgx_ctx *ctx, int64_t *counts);
 
 /* ---- diagonal preconditioning of a cgx_create_csr context (see "Sparse A" above) ------------- */
 #define CGX_PC_NONE   0
@@ -794,6 +878,9 @@ int cgx_spmm_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *co
 int cgx_spmm_csr_f32(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
                      const float *values, int nrhs, const void *V, int64_t ldv,
                      void *Out, int64_t ldo, void *stream);
+/* Kernel-level, device pointers: dst[idx[e]] = src[idx[e]] for e < count (doubles; idx int32,
+ * every value once, not range-checked).  The caller offsets dst. */
+int cgx_gather_indexed(const void *src, const void *idx, int64_t count, void *dst, void *stream);
 /* vecVec: *out_dev = a . b */
 int cgx_dot(int dtype, int64_t n, const void *a, const void *b, void *out_dev, void *stream);
 /* residual x2 + vecVec: r = b - Ax; p = b - Ax; *rr_dev = r.r (rr_dev may be NULL) */
