@@ -468,7 +468,7 @@ def _csr_checked(what: str, rp, ci, rows: int, cols: int) -> None:
 def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int, cols: int, *,
              a_f32: bool = False) -> None:
     """out[i] = sum_e data[e] * v[indices[e]] over row i's entries, in stored
-    order (k_spmv_csr_f64; the plan from CGX_SPMV_PLAN).  The structure comes
+    order (k_csr_mult_f64; the plan from CGX_SPMV_PLAN).  The structure comes
     as host arrays: it is checked (cgx_csr_check) and only then uploaded, so the
     kernel never sees an index outside v.  ``a_f32=True`` (cgx_spmv_csr_f32): data
     is cast to float32 and stays float32 on the device; the kernel widens it
@@ -494,7 +494,7 @@ def spmv_csr(indptr, indices, data, v: DeviceArray, out: DeviceArray, rows: int,
 
 def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int, cols: int, nrhs: int,
              ldv: int | None = None, ldo: int | None = None, *, a_f32: bool = False) -> None:
-    """``nrhs`` sparse matVecs in one pass over the CSR arrays (k_spmm_csr_f64; the plan from
+    """``nrhs`` sparse matVecs in one pass over the CSR arrays (k_csr_mult_f64; the plan from
     CGX_SPMM_PLAN): Out[j*ldo + i] = sum_e data[e] * V[j*ldv + indices[e]].  Column j is
     :func:`spmv_csr`'s result on column j of V bit for bit at the same T.  The structure is
     checked on the host before anything is uploaded, as :func:`spmv_csr` does.

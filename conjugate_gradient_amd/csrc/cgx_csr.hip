@@ -1,7 +1,7 @@
 // cgx_csr.hip -- cgx_create_csr contexts (cgx_ctx.h, OP_CSR): a general sparse
 // A in CSR storage on one GPU, fp64.  The context is a cgx_create context
 // without the dense A: its vectors, scalars, stream, events and iteration are
-// the same, and launch_matvec multiplies with k_spmv_csr_f64 (cgx_spmv.hip).
+// the same, and launch_matvec multiplies with k_csr_mult_f64 (cgx_csr_core.h).
 //
 // The kernel reads v[col_idx[e]] unchecked, so the structure is checked on the
 // host (cgx_csr_check) before anything is uploaded: no path of a context
@@ -36,11 +36,17 @@ int csr_need_matrix(const cgx_ctx *c, const char *what) {
     return CGX_OK;
 }
 
-int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
+int csr_plan_args(int K, int R, int U, int nt) {
     const bool r_ok = R == 1 || R == 2 || R == 4 || R == 8 || R == 16 || R == 32;
-    if (!r_ok || U != 1 || !spmv_csr_plan_ok(64 / R, nt))
-        return fail(CGX_ERR_ARG, "cgx_create_csr context: rows_per_wave (64 / T) must be 1, 2, 4, 8, 16 or 32, "
-                                 "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
+    if (!r_ok || U != 1 || !(K == 1 ? spmv_csr_plan_ok(64 / R, nt) : spmm_csr_plan_ok(K, 64 / R, nt)))
+        return fail(CGX_ERR_ARG, "%s context: rows_per_wave (64 / T) must be 1, 2, 4, 8, 16 or 32, "
+                                 "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)",
+                    K == 1 ? "cgx_create_csr" : "cgx_create_csr_nrhs", R, U, nt);
+    return CGX_OK;
+}
+
+int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
+    TRY(csr_plan_args(1, R, U, nt));
     for (auto &s : c->sh) {  // one T for every row block, each block's grid from its own rows
         TRY(set_dev(s));
         s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu,

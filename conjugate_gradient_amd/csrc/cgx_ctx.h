@@ -273,7 +273,7 @@ struct LocalPool;  // cgx_local_mt.hip
 // doubles (zero past n), so p is what k_matvec_nrhs_f64 multiplies.
 // cgx_create_csr_nrhs: the same state beside a cgx_create_csr context's shard
 // (op == OP_CSR: the CSR arrays instead of A); nrhs_matvec then multiplies with
-// k_spmm_csr_f64 (cgx_spmm.hip) and `plan` is plan_spmm_csr's.
+// k_csr_mult_f64 (cgx_csr_core.h, cgx_spmm.hip) and `plan` is plan_spmm_csr's.
 struct NrhsState {
     int nrhs = 0;  // 1..CGX_MAX_NRHS
     char *b = nullptr, *x = nullptr, *r = nullptr, *p = nullptr, *Ap = nullptr;
@@ -542,6 +542,8 @@ int nrhs_get_stats(cgx_ctx *c, cgx_stats *st);
 int nrhs_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu);
 // cgx_csr.hip
 int csr_need_matrix(const cgx_ctx *c, const char *what);  // CGX_ERR_STATE before the first cgx_set_csr
+// what cgx_set_matvec_plan accepts on a CSR context of width K (1: cgx_create_csr; 2, 4, 8: cgx_create_csr_nrhs)
+int csr_plan_args(int K, int R, int U, int nt);
 int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu);
 // cgx_api.hip
 int dev_ws(RedWs *out);

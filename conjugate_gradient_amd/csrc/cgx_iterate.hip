@@ -189,6 +189,10 @@ int do_begin(cgx_ctx *c) {
     // copied into pfull first -- one copy fewer per solve.
     const bool x_direct = f32ref(c) && c->mode == M_SINGLE && !(c->flags & CGX_HOST_STREAM);
     if (!zero && !x_direct) TRY(exchange_allgather(c, /*from_x=*/true));  // full x0 into pfull
+    // Poisson over several slabs of one process: exchange_halo put x0 into each slab's pown and the neighbours
+    // copy their halo rows out of it on their own streams; the residual kernel below writes p0 into that pown.
+    // Every stream waits for every slab's copies first.
+    if (!zero && c->op == OP_POISSON && c->mode == M_LOCAL) TRY(local_barrier(c));
     const int gs = S_RR + ring(0), ls = S_LRR + ring(0);
     const int os = out_slot(c, ls, gs);
     for (auto &s : c->sh) {
@@ -197,10 +201,8 @@ int do_begin(cgx_ctx *c) {
             TRY(launch_matvec(c, s, x_direct ? s.x : s.pfull, false, 0));
         s.x_zero = false;  // the iterations update x
         if (f32ref(c)) {
-            HIPT(residual_dot_ref_f32(s.nloc, reinterpret_cast<const float *>(s.b),
-                                      reinterpret_cast<const float *>(s.Ap), reinterpret_cast<float *>(s.r),
-                                      reinterpret_cast<float *>(s.pown), reinterpret_cast<float *>(slot(s, os)),
-                                      s.stream, reinterpret_cast<int64_t *>(slot(s, S_KDONE))));
+            HIPT(residual_dot_ref_f32(s.nloc, f32(s.b), f32(s.Ap), f32(s.r), f32(s.pown), slot_f32(s, os), s.stream,
+                                      slot_i64(s, S_KDONE)));
         } else if (c->pc_kind == CGX_PC_BLOCK) {
             // block Jacobi: p0 = W r0 block by block, and r0.z0 beside r0.r0
             HIPT(pcgb_residual_f64(c->pc_bs, s.nloc, f64(s.b), zero ? nullptr : f64(s.Ap), f64(s.pc_w), s.pc_wld,
@@ -213,11 +215,8 @@ int do_begin(cgx_ctx *c) {
         } else {
             // x0 = 0: Ax = nullptr (r = b - 0.0, no Ap buffer to clear); the
             // kernel also resets the convergence record (no memset launch)
-            double *pown = reinterpret_cast<double *>(s.pown);
-            HIPT(residual_f64(s.nloc, reinterpret_cast<const double *>(s.b),
-                              zero ? nullptr : reinterpret_cast<const double *>(s.Ap),
-                              reinterpret_cast<double *>(s.r), pown, reinterpret_cast<double *>(slot(s, os)), s.ws,
-                              s.stream, reinterpret_cast<int64_t *>(slot(s, S_KDONE))));
+            HIPT(residual_f64(s.nloc, f64(s.b), zero ? nullptr : f64(s.Ap), f64(s.r), f64(s.pown), slot_f64(s, os), s.ws,
+                              s.stream, slot_i64(s, S_KDONE)));
         }
     }
     TRY(exchange_scalar(c, ls, gs));
@@ -935,18 +934,12 @@ int cgx_residual_norm(cgx_ctx *c, double *rnorm, double *bnorm) {
         TRY(set_dev(s));
         TRY(launch_matvec(c, s, s.pfull, false, 0));
         if (f32ref(c)) {
-            HIPT(residual_ref_f32(s.nloc, reinterpret_cast<const float *>(s.b), reinterpret_cast<const float *>(s.Ap),
-                                  reinterpret_cast<float *>(s.r), nullptr, s.stream));
-            HIPT(dot_ref_f32(s.nloc, reinterpret_cast<const float *>(s.r), reinterpret_cast<const float *>(s.r),
-                             reinterpret_cast<float *>(slot(s, tro)), s.stream));
-            HIPT(dot_ref_f32(s.nloc, reinterpret_cast<const float *>(s.b), reinterpret_cast<const float *>(s.b),
-                             reinterpret_cast<float *>(slot(s, tbo)), s.stream));
+            HIPT(residual_ref_f32(s.nloc, f32(s.b), f32(s.Ap), f32(s.r), nullptr, s.stream));
+            HIPT(dot_ref_f32(s.nloc, f32(s.r), f32(s.r), slot_f32(s, tro), s.stream));
+            HIPT(dot_ref_f32(s.nloc, f32(s.b), f32(s.b), slot_f32(s, tbo), s.stream));
         } else {
-            HIPT(residual_f64(s.nloc, reinterpret_cast<const double *>(s.b), reinterpret_cast<const double *>(s.Ap),
-                              reinterpret_cast<double *>(s.r), nullptr, reinterpret_cast<double *>(slot(s, tro)), s.ws,
-                              s.stream));
-            HIPT(dot_f64(s.nloc, reinterpret_cast<const double *>(s.b), reinterpret_cast<const double *>(s.b),
-                         reinterpret_cast<double *>(slot(s, tbo)), s.ws, s.stream));
+            HIPT(residual_f64(s.nloc, f64(s.b), f64(s.Ap), f64(s.r), nullptr, slot_f64(s, tro), s.ws, s.stream));
+            HIPT(dot_f64(s.nloc, f64(s.b), f64(s.b), slot_f64(s, tbo), s.ws, s.stream));
         }
     }
     TRY(exchange_scalar(c, S_LTR, S_TR));

@@ -85,7 +85,7 @@ struct MatvecPlan {
     int small = 0;    // > 0: k_matvec_small_f64 with this many threads per block (vector in LDS)
     int a32 = 0;      // 1: k_matvec_a32's plan (float A; U counts 256-column chunks, nt is 2 or 8)
     int nrhs = 0;     // > 0: k_matvec_nrhs_f64's plan for this many vectors per pass (2, 4 or 8; nt is 2 or 8)
-    int csr = 0;      // 1: k_spmv_csr_f64's plan (R = 64 / T rows per wave, U = 1, nt is 2 or 8)
+    int csr = 0;      // 1: k_csr_mult_f64's plan (R = 64 / T rows per wave, U = 1, nt is 2 or 8)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -207,7 +207,7 @@ hipError_t nrhs_update_xp_f64(int64_t n, int64_t ld, int nrhs, int64_t k, double
 // ---- sparse A in CSR storage (cgx_spmv.hip) --------------------------------------
 // out[i] = sum over e in [row_ptr[i], row_ptr[i+1]) of values[e] * v[col_idx[e]],
 // entries in stored order, T = 64 / pl.R lanes per row (the order contract is
-// in cgx_spmv.hip); pown != nullptr: also *dot_out = pown . out (fixed order
+// in cgx_csr_core.h); pown != nullptr: also *dot_out = pown . out (fixed order
 // for a fixed grid).  The indices are not range-checked here (cgx_csr_check).
 // The instantiated (T, policy): T in {2, 4, 8, 16, 32, 64}, policy 2 or 8.
 bool spmv_csr_plan_ok(int T, int nt);
@@ -235,11 +235,12 @@ hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int3
 // ---- several right-hand sides on a CSR matrix (cgx_spmm.hip) ----------------------
 // Out[j*ldo + i] = sum over row i's entries of values[e] * V[j*ldv + col_idx[e]]
 // for j < nrhs: values and col_idx loaded once per entry and multiplied by
-// K = nrhs_width(nrhs) gathered elements.  Each column sums in k_spmv_csr_f64's
-// order at the same T = 64 / pl.R, so it is spmv_csr_f64's result on that
-// column bit for bit.  pown != nullptr: also dot_out[j] = pown[j*ldp ..] .
-// Out[j*ldo ..] for every j < nrhs (ws as the nrhs kernels': kMaxNrhs *
-// kMaxRedBlocks partials).  The indices are not range-checked here.
+// K = nrhs_width(nrhs) gathered elements.  Each column sums in spmv_csr_f64's
+// order at the same T = 64 / pl.R (both are k_csr_mult_f64, cgx_csr_core.h), so
+// it is spmv_csr_f64's result on that column bit for bit.  pown != nullptr:
+// also dot_out[j] = pown[j*ldp ..] . Out[j*ldo ..] for every j < nrhs (ws as
+// the nrhs kernels': kMaxNrhs * kMaxRedBlocks partials).  The indices are not
+// range-checked here.
 // The instantiated (K, T, policy): K in {2, 4, 8}, T in {2, .., 64}, policy 2 or 8.
 bool spmm_csr_plan_ok(int K, int T, int nt);
 // T <= 0 / nt < 0 / blocks_per_cu <= 0 pick the defaults (T from the mean row

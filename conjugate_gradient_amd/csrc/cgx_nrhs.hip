@@ -318,10 +318,7 @@ int nrhs_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
     NrhsState *nr = c->nr;
     const int K = nrhs_width(nr->nrhs);
     if (c->op == OP_CSR) {  // cgx_create_csr_nrhs: csr_set_plan's rule
-        const bool r_ok = R == 1 || R == 2 || R == 4 || R == 8 || R == 16 || R == 32;
-        if (!r_ok || U != 1 || !spmm_csr_plan_ok(K, 64 / R, nt))
-            return fail(CGX_ERR_ARG, "cgx_create_csr_nrhs context: rows_per_wave (64 / T) must be 1, 2, 4, 8, 16 or 32, "
-                                     "chunks_in_flight 1 and the load policy 2 or 8 (got %d, %d, %d)", R, U, nt);
+        TRY(csr_plan_args(K, R, U, nt));
         TRY(set_dev(c->sh[0]));
         nr->plan = plan_spmm_csr(c->sh[0].dev, c->sh[0].nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, K, 64 / R, nt,
                                  blocks_per_cu, c->csr_f32);

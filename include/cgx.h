@@ -102,7 +102,7 @@
  *     entries [row_ptr[i], row_ptr[i+1]).
  *   - Entries are taken in stored order: columns need not be sorted, and a
  *     duplicate column is two terms of the sum.  An empty row gives +0.0.
- *   - Summation order (k_spmv_csr_f64, T lanes per row, T = 2 .. 64): with
+ *   - Summation order (k_csr_mult_f64, T lanes per row, T = 2 .. 64): with
  *     s = row_ptr[i], sub-lane l starts from +0.0 and adds entries s+l,
  *     s+l+T, s+l+2T, ... in that order with one fp64 FMA each; the T partial
  *     sums are combined as v[l] += v[l ^ o] for o = T/2, ..., 1.  A row's sum
@@ -211,7 +211,7 @@
  *       element).
  *   - Several right-hand sides (cgx_create_csr_nrhs): nrhs (1..CGX_MAX_NRHS)
  *     systems A x_j = b_j on one CSR matrix, the CSR arrays read once per
- *     iteration (k_spmm_csr_f64).  The context is a cgx_create_csr context's
+ *     iteration (k_csr_mult_f64).  The context is a cgx_create_csr context's
  *     matrix with a cgx_create_nrhs context's vectors, scalars and loop.
  *     - Order per column: exactly the one above at the same T.  Column j of a
  *       product is cgx_spmv_csr's result on column j bit for bit; it does not

@@ -1,4 +1,4 @@
-"""The summation order of k_spmv_csr_f64 (cgx_spmv.hip), on the CPU.
+"""The summation order of k_csr_mult_f64 (cgx_csr_core.h), on the CPU.
 
 An exact emulation of the order contract include/cgx.h states, independent of
 the GPU code: every (T, load policy, grid) of the kernel must give these bits.
@@ -76,6 +76,44 @@ def spmv_csr(indptr, indices, data, v, T):
     return out
 
 
+def _butterfly64(lanes):
+    """wave_sum on every row of an (m, 64) array: lanes[:, l] += lanes[:, l ^ o] for o = 32, ..., 1."""
+    o = 32
+    while o:
+        lanes = lanes + lanes[:, np.arange(64) ^ o]
+        o >>= 1
+    return lanes[:, 0]
+
+
+def fused_dot(out, p, T, blocks):
+    """The kernel's fused dot p . out on a grid of `blocks` blocks of 4 waves, for terms p[i] * out[i] that are
+    exact in fp64 (p signed powers of two), so that every step is one correctly rounded add.  Wave w of the grid
+    takes the row groups w, w + 4 blocks, ...; the lane that stores row i of a group adds its term to its own sum
+    (from +0.0, in that order); then wave_sum, the block's four waves in order, and grid_sum_last_block's sum of the
+    block totals: one block stores 0.0 + its total; otherwise thread t of the last block adds the totals t, t + 256,
+    ... in that order, then wave_sum and the four waves in order again."""
+    RW, W = 64 // T, 4 * blocks
+    term = np.asarray(p, np.float64) * out
+    sweeps = -(-(-(-term.size // RW)) // W)
+    rows = np.zeros(sweeps * W * RW)
+    rows[:term.size] = term
+    acc = np.zeros((W, RW))
+    for part in rows.reshape(sweeps, W, RW):
+        acc = acc + part
+    lanes = np.zeros((W, 64))
+    lanes[:, ::T] = acc  # the storing lane of row r of the group is lane r T
+    red = _butterfly64(lanes).reshape(blocks, 4)
+    tot = ((red[:, 0] + red[:, 1]) + red[:, 2]) + red[:, 3]
+    if blocks == 1:
+        return 0.0 + tot[0]
+    assert blocks <= 8192
+    s = np.zeros(256)
+    for i0 in range(0, blocks, 256):
+        s[:tot[i0:i0 + 256].size] += tot[i0:i0 + 256]
+    red = _butterfly64(s.reshape(4, 64))
+    return ((red[0] + red[1]) + red[2]) + red[3]
+
+
 def exact_rows(indptr, indices, data, v):
     """Per row: (the correctly rounded exact sum, sum of |terms| as a float, the entry count)."""
     res = []
@@ -99,10 +137,11 @@ def tridiag(n):
     return indptr, cols[keep].astype(np.int32), vals[keep]
 
 
-def spmv_tridiag(n, v, T):
+def spmv_tridiag(n, v, T, csr=None):
     """spmv_csr on tridiag(n), vectorised over the rows.  A row has at most 3 entries: with T >= 4 every sub-lane
-    holds at most one (exact) product, with T = 2 sub-lane 0 holds entry 0 and then entry 2."""
-    indptr, indices, data = tridiag(n)
+    holds at most one (exact) product, with T = 2 sub-lane 0 holds entry 0 and then entry 2.  csr: a matrix of
+    tridiag(n)'s structure with other values, for a v that keeps the products exact."""
+    indptr, indices, data = csr or tridiag(n)
     lens = np.diff(indptr)
     prod = np.zeros((n, 3))  # the exact product of entry k of row i, +0.0 where the row is shorter
     for k in range(3):

@@ -1,6 +1,6 @@
-"""cgx_create_csr: a sparse A in CSR storage (k_spmv_csr_f64, cgx_spmv.hip) through every layer -- the kernel's
-bits against the CPU statement of its summation order (tests/_spmv_order.py), the context's plans and host forms,
-solves against the oracle, the Poisson matrix against the matrix-free operator, the refusals and `cg_hip --csr`.
+"""cgx_create_csr: a sparse A in CSR storage (k_csr_mult_f64 at K = 1, cgx_csr_core.h) through every layer -- the
+kernel's bits against the CPU statement of its summation order (tests/_spmv_order.py), the context's plans and host
+forms, solves against the oracle, the Poisson matrix against the matrix-free operator, the refusals and `cg_hip --csr`.
 
 Masked systems: A = oracle.spd_hash(n, seed)[0] with every entry zeroed except where |i-j| <= 2, or
 (i+j) % 7 == 0 and |i-j| <= 64, or i % 50 == 0, or j % 50 == 0 (symmetric; the diagonal keeps A positive definite;
@@ -185,6 +185,32 @@ def test_one_row(monkeypatch, T):
     assert same_bits(out, [-3.75])
     out = run_kernel(np.array([0, 0], np.int64), np.zeros(0, np.int32), np.zeros(0), np.array([-1.25]), 1, 1)
     assert same_bits(out, [0.0])  # an empty row stores +0.0
+
+
+@pytest.mark.parametrize("n,one_block", [(29, True), (70001, False)])
+def test_fused_dot_bits(n, one_block):
+    """The fused p.Ap of a context's SpMV against the CPU statement (so.fused_dot), on a one-block grid (29 rows at
+    T = 8: four row groups) and on one of more than 256 blocks that wraps (70,001 rows: 8,751 groups).  A context
+    does not hand out p.Ap; the first iteration from x0 = 0 shows it: p0 = r0 = b, x1 = alpha b with
+    alpha = r0.r0 / p0.Ap0.  b holds signed powers of two, so r0.r0 is exact in any order, b[i] * Ap[i] is exact
+    (an FMA onto a sum is one rounded add, as the statement needs) and x1[i] / b[i] is alpha's bits; the matrix
+    values are normal, so the sums round and their order shows."""
+    T = 8
+    rng = np.random.default_rng(n)
+    indptr, indices, _ = so.tridiag(n)
+    csr = (indptr, indices, rng.standard_normal(indices.size))
+    b = rng.choice([-1.0, 1.0], n) * 2.0 ** rng.integers(-1, 2, n)
+    with csr_solver(csr, b) as s:
+        s.set_matvec_plan(64 // T, 1, 2)
+        blocks = s.matvec_plan()["blocks"]
+        assert (blocks == 1) if one_block else (blocks > 256 and 4 * blocks * (64 // T) < n), blocks
+        s.begin()
+        assert s.iterate(1, eps=-1.0) == (1, False)
+        x = s.get_x()
+    pap = so.fused_dot(so.spmv_tridiag(n, b, T, csr), b, T, blocks)
+    alpha = float(b @ b) / pap
+    print(f"n={n} blocks={blocks} p.Ap={pap!r} alpha={alpha!r} got={x[0] / b[0]!r}")
+    assert same_bits(x / b, np.full(n, alpha)), (blocks, alpha, x[0] / b[0])
 
 
 # ---- 3. context plans ----------------------------------------------------------------------------------------

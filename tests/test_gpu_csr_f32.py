@@ -1,4 +1,4 @@
-"""cgx_set_csr_f32: float-stored CSR values with fp64 arithmetic (k_spmv_csr_f64 / k_spmm_csr_f64 with VT = float,
+"""cgx_set_csr_f32: float-stored CSR values with fp64 arithmetic (k_csr_mult_f64 with VT = float,
 k_csr_diag_minv, k_csr_diag_blocks) through every layer.
 
 The contract is bit equality, so no test here has a tolerance: widening a float is exact and the summation order

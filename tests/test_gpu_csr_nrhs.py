@@ -1,4 +1,4 @@
-"""cgx_create_csr_nrhs: several right-hand sides on one CSR matrix (k_spmm_csr_f64, cgx_spmm.hip) through every
+"""cgx_create_csr_nrhs: several right-hand sides on one CSR matrix (k_csr_mult_f64 at K = 2, 4, 8, cgx_csr_core.h) through every
 layer -- the kernel's bits per column against the CPU statement of the SpMV's summation order
 (tests/_spmv_order.py) and against cgx_spmv_csr itself, the context's plans, per-column solves against the oracle,
 the freeze rule, the host forms, the Poisson matrix and the refusals.

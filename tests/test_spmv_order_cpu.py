@@ -1,5 +1,7 @@
-"""The CPU statement of k_spmv_csr_f64's summation order (tests/_spmv_order.py), checked against exact
+"""The CPU statement of k_csr_mult_f64's summation order (tests/_spmv_order.py), checked against exact
 arithmetic, so the GPU test (test_gpu_csr.py) compares the kernel with something that is itself verified."""
+import math
+
 import numpy as np
 import pytest
 
@@ -78,3 +80,25 @@ def test_vectorised_tridiagonal_emulation_equals_the_general_one(T):
     assert np.array_equal(got, want) and np.array_equal(np.signbit(got), np.signbit(want))
     assert tuple(np.diff(so.tridiag(n)[0])[[0, 1, -1]]) == (2, 3, 2)
     assert so.spmv_tridiag(1, v[:1], T)[0] == so.spmv_csr(*so.tridiag(1), v[:1], T)[0] == 2.0 * v[0]
+
+
+@pytest.mark.parametrize("T,blocks,n", [(8, 1, 29), (8, 3, 1000), (2, 300, 70001), (64, 2048, 9000)])
+def test_fused_dot_counts_every_row_once_and_shows_the_order(T, blocks, n):
+    rng = np.random.default_rng(n)
+    p = rng.choice([-1.0, 1.0], n) * 2.0 ** rng.integers(-1, 2, n)
+    whole = rng.integers(-1000, 1000, n).astype(np.float64)  # every partial sum is exact: the order cannot show
+    assert so.fused_dot(whole, p, T, blocks) == float(np.sum(p * whole))
+    out = rng.standard_normal(n)
+    got = so.fused_dot(out, p, T, blocks)
+    assert abs(got - math.fsum(p * out)) <= 2.0 ** -52 * n * float(np.abs(p * out).max())
+    if n > 1000:  # another grid is another order
+        assert got != so.fused_dot(out, p, T, blocks + 1) or got != so.fused_dot(out, p, T, blocks + 2)
+
+
+def test_tridiagonal_emulation_with_other_values():
+    n, T = 203, 8
+    rng = np.random.default_rng(6)
+    indptr, indices, _ = so.tridiag(n)
+    csr = (indptr, indices, rng.standard_normal(indices.size))
+    v = 2.0 ** rng.integers(-1, 2, n)
+    assert np.array_equal(so.spmv_tridiag(n, v, T, csr), so.spmv_csr(*csr, v, T))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Sweep every instantiated plan (T lanes per row, load policy) of the several-right-hand-sides CSR kernel
-k_spmm_csr_f64 at K = 2, 4, 8 on one GPU, against the one-system cgx_create_csr context under its default plan,
+k_csr_mult_f64 at K = 2, 4, 8 on one GPU, against the one-system cgx_create_csr context under its default plan,
 interleaved in the same rounds in one process.
 
 The two matrices are tools/spmv_ab.py's, built with numpy from nothing but their sizes:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Sweep every instantiated plan (T lanes per row, load policy) of the CSR SpMV kernel k_spmv_csr_f64 on one GPU,
-against the vendor library's CSR product reached through torch (torch.sparse_csr_tensor(...) @ v), in interleaved
-rounds in one process.
+"""Sweep every instantiated plan (T lanes per row, load policy) of the CSR SpMV kernel (k_csr_mult_f64 at K = 1) on one
+GPU, against the vendor library's CSR product reached through torch (torch.sparse_csr_tensor(...) @ v), in
+interleaved rounds in one process.
 
 Two matrices, built with numpy from nothing but their sizes:
   poisson  the 5-point matrix of an m x m grid (default m = 4096: 16.8 M rows, 83.9 M entries, mean row length 5)
@@ -13,11 +13,12 @@ and the torch product run once, --iters launches each after one warm launch.  Th
 context's CGX_TIMING events (torch: torch.cuda events around the same number of products); the iteration by
 fixed-count iterations bracketed by synchronize.  One JSON line per round and configuration, then one summary
 line with the medians, the round-to-round spread and the default plan's ratio to torch.  GB/s are on the
-algorithmic bytes 12 nnz + 8 (n + 1) + 16 n.  For poisson the matrix-free Solver(poisson_m=m) iteration rate is
-recorded too (context, not a target: it moves 58.7 B per point).
+algorithmic bytes 12 nnz + 8 (n + 1) + 16 n (8 nnz with --a-f32).  For poisson the matrix-free
+Solver(poisson_m=m) iteration rate is recorded too (context, not a target: it moves 58.7 B per point).
 
   python tools/spmv_ab.py --matrix poisson [--m 4096] [--rounds 5] [--iters 20] [--out profiles/spmv_ab_poisson.jsonl]
   python tools/spmv_ab.py --matrix banded [--logn 20] [--hb 32]
+  --a-f32: float-stored values (cgx_set_csr_f32; the values are rounded to float first, for torch too)
 """
 import argparse
 import json
@@ -134,6 +135,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--settle", type=float, default=2.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--a-f32", action="store_true", help="float-stored values (cgx_set_csr_f32)")
     ap.add_argument("--torch-first", action="store_true",
                     help="initialise torch's GPU runtime before libcgx is loaded (a torch wheel that bundles its own "
                          "HIP runtime finds no GPU once another copy of the runtime has opened the device)")
@@ -148,8 +150,10 @@ def main():
     else:
         indptr, indices, data = banded_csr(1 << args.logn, args.hb)
         label = f"banded n=2^{args.logn} hb={args.hb}"
+    if args.a_f32:
+        data = data.astype(np.float32).astype(np.float64)
     n, nnz = indptr.size - 1, int(indptr[-1])
-    abytes = 12 * nnz + 8 * (n + 1) + 16 * n
+    abytes = (8 if args.a_f32 else 12) * nnz + 8 * (n + 1) + 16 * n
     build_s = time.perf_counter() - t0
 
     def gbs(ms):
@@ -162,7 +166,7 @@ def main():
             torch.cuda.synchronize()
     if cg.device_count() < 1:
         sys.exit("no GPU visible: nothing is measured")
-    s = cg.Solver.from_csr(indptr, indices, data, flags=cg.CGX_F64 | cg.CGX_TIMING)
+    s = cg.Solver.from_csr(indptr, indices, data, flags=cg.CGX_F64 | cg.CGX_TIMING, a_f32=args.a_f32)
     default = s.matvec_plan()
     default_plan = (64 // default["R"], default["nt"])
     tc, torch_note = torch_setup(indptr, indices, data, n)
@@ -170,7 +174,7 @@ def main():
     if tc is not None:  # the same product at the timed size: the kernel against the vendor library
         dv, do = cg.DeviceArray.from_host(np.ones(n)), cg.DeviceArray(n)
         os.environ["CGX_SPMV_PLAN"] = f"T={default_plan[0]},nt={default_plan[1]}"
-        cg.spmv_csr(indptr, indices, data, dv, do, n, n)
+        cg.spmv_csr(indptr, indices, data, dv, do, n, n, a_f32=args.a_f32)
         del os.environ["CGX_SPMV_PLAN"]
         mine, theirs = do.to_host(), tc[3].cpu().numpy()
         check = float(np.max(np.abs(mine - theirs)) / max(np.max(np.abs(theirs)), 1e-300))
@@ -193,7 +197,8 @@ def main():
             f.flush()
             print(json.dumps(rec), flush=True)
 
-        emit({"record": "setup", "matrix": label, "n": n, "nnz": nnz, "algorithmic_bytes": abytes,
+        emit({"record": "setup", "matrix": label, "values": "float" if args.a_f32 else "double", "n": n, "nnz": nnz,
+              "algorithmic_bytes": abytes,
               "build_s": round(build_s, 2), "default_plan": {"T": default_plan[0], "nt": default_plan[1],
                                                              "blocks": default["blocks"]},
               "torch": torch_note, "max_rel_diff_vs_torch": check, "rounds": args.rounds, "iters": args.iters})
