@@ -374,21 +374,9 @@ __device__ __forceinline__ void stv(double *p, d2 v) {
     else *reinterpret_cast<d2 *>(p) = v;
 }
 
-// Vector kernels.  VEC (every pointer 16-B aligned): a block step covers
-// kVU * kNT consecutive element pairs; each thread loads its kVU pairs of
-// every input (16-B loads, all issued before any store), computes, stores.
-// Otherwise a scalar grid-stride loop.  The odd tail element of the VEC
-// path is done by thread 0 of block 0.  Per-thread sums run in a fixed
-// order, then the deterministic grid reduction.
+// Vector kernels (vec_pass, cgx_vector_core.h): pairs per thread and block
+// step of the 16-B form; grid_vec below sizes the grid by it.
 constexpr int kVU = 4;
-
-#define CGX_VEC_LOOP_BEGIN                                                                   \
-    const int64_t npairs = n >> 1;                                                           \
-    const int64_t step = (int64_t)gridDim.x * kNT * kVU;                                     \
-    for (int64_t base = (int64_t)blockIdx.x * kNT * kVU + threadIdx.x; base < npairs; base += step) { \
-        bool ok[kVU];                                                                        \
-        _Pragma("unroll") for (int u = 0; u < kVU; ++u) ok[u] = base + u * kNT < npairs;
-#define CGX_VEC_LOOP_END }
 
 // The device-side stopping decision of k_update_xp_f64 / k_poisson_p_f64
 // (serialConjugate.c:235): eps < 0 disables it; kdone / rrfinal are device
@@ -400,6 +388,9 @@ struct ConvArgs {
     double *rrfinal = nullptr;
     int64_t *hrec = nullptr;    // host-mapped copy of {kdone, rrfinal}: read by the host without a copy
 };
+inline ConvArgs conv_args(double eps, int64_t k, int64_t *kdone, double *rrfinal, int64_t *hrec) {
+    return ConvArgs{eps, k, kdone, rrfinal, hrec};
+}
 
 // The convergence record: device slots for later launches' gates, and the
 // host-mapped copy the host reads after an event (no per-iteration D2H copy).
@@ -410,6 +401,27 @@ __device__ __forceinline__ void record_convergence(const ConvArgs &cv, int64_t k
         __hip_atomic_store(cv.hrec + 1, __double_as_longlong(rr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(cv.hrec, kdone, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+// The gated stop decision of the x/p kernels, at the top of the launch of
+// loop iteration cv.k (every block decides alike).  An earlier iteration
+// converged (kdone in (0, k]): the launch does nothing (!live), and rr_of()
+// -- the launch's r.r, which may be a folded peer sum that stores -- is not
+// called.  Otherwise rr = rr_of(); with gating on (cv.kdone) and
+// sqrt(rr) < eps, p is not updated and block 0 records k + 1 and rr.
+struct StopStep {
+    bool live, upd_p;
+    double rr;
+};
+template <class RR>
+__device__ __forceinline__ StopStep gated_stop(const ConvArgs &cv, bool upd_p, RR rr_of) {
+    if (cv.kdone && *cv.kdone != 0 && *cv.kdone <= cv.k) return {false, false, 0.0};
+    const double rr = rr_of();
+    if (cv.kdone && cv.eps >= 0.0 && sqrt(rr) < cv.eps) {
+        upd_p = false;
+        if (blockIdx.x == 0 && threadIdx.x == 0) record_convergence(cv, cv.k + 1, rr);
+    }
+    return {true, upd_p, rr};
 }
 
 // ---------------------------------------------------------------------------

@@ -7,41 +7,24 @@
 // from the minv and r they read anyway.  r.r and r.z come out of one pass
 // (grid_sum_last_block_n<2>: each summed as the one-value reduction sums it).
 //
-// Contraction contract.  Every kernel below runs with fp contraction off and
-// spells its fused operations out, in the shapes hipcc gives the plain
-// kernels (cgx_vector.hip, read off their gfx950 ISA):
-//   r_i   = fma(-alpha, Ap_i, r_i)               k_update_r_f64
-//   x_i   = fma(alpha, p_i, x_i)                 k_update_xp_f64
+// Contraction contract.  Every kernel below is a vec_pass (cgx_vector_core.h)
+// whose body runs with fp contraction off (the pragma stands inside each
+// body: it is lexical) and spells its fused operations out with the header's
+// vfma / vmul / dot_acc, in the shapes hipcc gives the plain kernels' single
+// spellings there (sub_r, axpy_x, next_p, elem_dot; read off the gfx950 ISA
+// of cgx_vector.hip):
+//   r_i   = fma(-alpha, Ap_i, r_i)               sub_r
+//   x_i   = fma(alpha, p_i, x_i)                 axpy_x
 //   z_i   = minv_i * r_i                         a rounded product
-//   p_i   = fma(beta, p_i, z_i)                  k_update_xp_f64's, z for r
-//   pair  : acc = acc + fma(a.x, b.x, a.y * b.y) r.r's, and r.z with b = z
+//   p_i   = fma(beta, p_i, z_i)                  next_p, z for r
+//   pair  : acc = acc + fma(a.x, b.x, a.y * b.y) acc += elem_dot: r.r's, and r.z with b = z
 //   tail  : acc = fma(a, b, acc)                 the odd last element
 // so minv == 1 gives the plain kernels' bits, and minv == a power of two the
 // same x (alpha absorbs 1 / c, p absorbs c).
-#include "cgx_device.h"
+#include "cgx_vector_core.h"
 
 namespace cgx {
 namespace {
-
-__device__ __forceinline__ d2 fma2(double a, d2 b, d2 c) {
-    d2 o;
-    o.x = __builtin_fma(a, b.x, c.x);
-    o.y = __builtin_fma(a, b.y, c.y);
-    return o;
-}
-__device__ __forceinline__ d2 mul2(d2 a, d2 b) {
-#pragma clang fp contract(off)
-    d2 o;
-    o.x = a.x * b.x;
-    o.y = a.y * b.y;
-    return o;
-}
-// acc + (a.x b.x + a.y b.y) as the plain kernels' `acc += ri.x * ri.x + ri.y * ri.y` compiles
-__device__ __forceinline__ double pair_acc(double acc, d2 a, d2 b) {
-#pragma clang fp contract(off)
-    const double t = a.y * b.y;
-    return acc + __builtin_fma(a.x, b.x, t);
-}
 
 // r = b - A x (Ax == nullptr: b - 0.0), p = minv o r, out[0] = r.r,
 // out[stride] = r.z; block 0 resets the convergence record (k_residual_f64).
@@ -53,36 +36,16 @@ __global__ __launch_bounds__(kNT) void k_pcg_residual_f64(int64_t n, const doubl
 #pragma clang fp contract(off)
     if (clear2 && blockIdx.x == 0 && threadIdx.x < 2) clear2[threadIdx.x] = 0;
     double acc[2] = {0.0, 0.0};
-    CGX_VEC_LOOP_BEGIN
-    d2 bv[kVU], av[kVU], mv[kVU];
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            bv[u] = ld2(b + i);
-            av[u] = Ax ? ld2(Ax + i) : (d2)(0.0);
-            mv[u] = ld2(minv + i);
-        }
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            const d2 ri = bv[u] - av[u];
-            const d2 zi = mul2(mv[u], ri);
-            st2(r + i, ri);
-            st2(p + i, zi);
-            acc[0] = pair_acc(acc[0], ri, ri);
-            acc[1] = pair_acc(acc[1], ri, zi);
-        }
-    CGX_VEC_LOOP_END
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double ri = b[n - 1] - (Ax ? Ax[n - 1] : 0.0);
-        const double zi = minv[n - 1] * ri;
-        r[n - 1] = ri;
-        p[n - 1] = zi;
-        acc[0] = __builtin_fma(ri, ri, acc[0]);
-        acc[1] = __builtin_fma(ri, zi, acc[1]);
-    }
+    const auto body = [&](int64_t i, auto io, auto bv, auto av, auto mv) {
+#pragma clang fp contract(off)
+        const auto ri = bv - av;
+        const auto zi = vmul(mv, ri);
+        io.st(r + i, ri);
+        io.st(p + i, zi);
+        acc[0] = dot_acc(acc[0], ri, ri);
+        acc[1] = dot_acc(acc[1], ri, zi);
+    };
+    vec_pass<true, 0>(n, body, vin(b), vopt(Ax, Ax != nullptr), vin(minv));
     grid_sum_last_block_n<2>(acc, partials, ticket, out, 3u, stride);
 }
 
@@ -97,33 +60,15 @@ __global__ __launch_bounds__(kNT) void k_pcg_update_r_f64(int64_t n, double *__r
     if (gate && *gate) return;
     const double nalpha = -cg_ratio(*rz_old, *pAp);
     double acc[2] = {0.0, 0.0};
-    CGX_VEC_LOOP_BEGIN
-    d2 rv[kVU], av[kVU], mv[kVU];
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            rv[u] = ldv<2>(r + i);
-            av[u] = ldv<2>(Ap + i);
-            mv[u] = ldv<2>(minv + i);
-        }
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const d2 ri = fma2(nalpha, av[u], rv[u]);
-            const d2 zi = mul2(mv[u], ri);
-            stv<2>(r + 2 * (base + u * kNT), ri);
-            acc[0] = pair_acc(acc[0], ri, ri);
-            acc[1] = pair_acc(acc[1], ri, zi);
-        }
-    CGX_VEC_LOOP_END
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double ri = __builtin_fma(nalpha, Ap[n - 1], r[n - 1]);
-        const double zi = minv[n - 1] * ri;
-        r[n - 1] = ri;
-        acc[0] = __builtin_fma(ri, ri, acc[0]);
-        acc[1] = __builtin_fma(ri, zi, acc[1]);
-    }
+    const auto body = [&](int64_t i, auto io, auto rv, auto av, auto mv) {
+#pragma clang fp contract(off)
+        const auto ri = vfma(nalpha, av, rv);
+        const auto zi = vmul(mv, ri);
+        io.st(r + i, ri);
+        acc[0] = dot_acc(acc[0], ri, ri);
+        acc[1] = dot_acc(acc[1], ri, zi);
+    };
+    vec_pass<true, 2>(n, body, vin(r), vin(Ap), vin(minv));
     grid_sum_last_block_n<2>(acc, partials, ticket, out, 3u, stride);
 }
 
@@ -137,47 +82,18 @@ __global__ __launch_bounds__(kNT) void k_pcg_update_xp_f64(int64_t n, double *__
                                                            const double *pAp, const double *rr, const double *rz_new,
                                                            ConvArgs cv) {
 #pragma clang fp contract(off)
-    bool upd_p = rr != nullptr;
-    if (cv.kdone && *cv.kdone != 0 && *cv.kdone <= cv.k) return;
-    if (cv.kdone) {
-        const double rrn = rr ? *rr : 0.0;
-        if (cv.eps >= 0.0 && sqrt(rrn) < cv.eps) {
-            upd_p = false;
-            if (blockIdx.x == 0 && threadIdx.x == 0) record_convergence(cv, cv.k + 1, rrn);
-        }
-    }
+    const StopStep st = gated_stop(cv, rr != nullptr, [&] { return rr ? *rr : 0.0; });
+    if (!st.live) return;
+    const bool upd_p = st.upd_p;
     const double rzo = *rz_old;
     const double alpha = cg_ratio(rzo, *pAp);
     const double beta = upd_p ? cg_ratio(*rz_new, rzo) : 0.0;
-    CGX_VEC_LOOP_BEGIN
-    d2 xv[kVU], pv[kVU], rv[kVU], mv[kVU];
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            xv[u] = ldv<2>(x + i);
-            pv[u] = ldv<2>(p + i);
-            if (upd_p) {
-                rv[u] = ldv<2>(r + i);
-                mv[u] = ldv<2>(minv + i);
-            }
-        }
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            stv<2>(x + i, fma2(alpha, pv[u], xv[u]));
-            if (upd_p) stv<2>(p + i, fma2(beta, pv[u], mul2(mv[u], rv[u])));
-        }
-    CGX_VEC_LOOP_END
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double pi = p[n - 1];
-        x[n - 1] = __builtin_fma(alpha, pi, x[n - 1]);
-        if (upd_p) {
-            const double zi = minv[n - 1] * r[n - 1];
-            p[n - 1] = __builtin_fma(beta, pi, zi);
-        }
-    }
+    const auto body = [&](int64_t i, auto io, auto xv, auto pv, auto rv, auto mv) {
+#pragma clang fp contract(off)
+        io.st(x + i, vfma(alpha, pv, xv));
+        if (upd_p) io.st(p + i, vfma(beta, pv, vmul(mv, rv)));
+    };
+    vec_pass<true, 2>(n, body, vin(x), vin(p), vopt(r, upd_p), vopt(minv, upd_p));
 }
 
 // One-time set-up, one row per lane: d_i = the sum, from +0.0 in stored order,
@@ -233,12 +149,7 @@ hipError_t pcg_update_xp_f64(int64_t n, double *x, double *p, const double *r, c
                              const double *rz_old, const double *pAp, const double *rr, const double *rz_new,
                              hipStream_t s, double eps, int64_t k, int64_t *kdone, double *rrfinal, int64_t *hrec) {
     if (!(al16(x) && al16(p) && al16(r) && al16(minv))) return hipErrorInvalidValue;
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(k_pcg_update_xp_f64, dim3(grid_vec(n)), dim3(kNT), 0, s, n, x, p, r, minv, rz_old, pAp, rr,
                        rz_new, cv);
     return hipGetLastError();

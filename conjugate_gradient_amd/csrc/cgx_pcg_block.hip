@@ -24,7 +24,7 @@
 //           rows in ascending order, then grid_sum_last_block_n<2> -- fixed for
 //           a given (n, BS); not the diagonal kernels' order.
 // The short last block (t = n % BS rows) uses its leading t x t entries only.
-#include "cgx_device.h"
+#include "cgx_vector_core.h"
 
 namespace cgx {
 namespace {
@@ -174,48 +174,18 @@ __global__ __launch_bounds__(kNT) void k_pcgb_update_xp_f64(int64_t n, double *_
                                                             const double *pAp, const double *rr, const double *rz_new,
                                                             ConvArgs cv) {
 #pragma clang fp contract(off)
-    bool upd_p = rr != nullptr;
-    if (cv.kdone && *cv.kdone != 0 && *cv.kdone <= cv.k) return;
-    if (cv.kdone) {
-        const double rrn = rr ? *rr : 0.0;
-        if (cv.eps >= 0.0 && sqrt(rrn) < cv.eps) {
-            upd_p = false;
-            if (blockIdx.x == 0 && threadIdx.x == 0) record_convergence(cv, cv.k + 1, rrn);
-        }
-    }
+    const StopStep st = gated_stop(cv, rr != nullptr, [&] { return rr ? *rr : 0.0; });
+    if (!st.live) return;
+    const bool upd_p = st.upd_p;
     const double rzo = *rz_old;
     const double alpha = cg_ratio(rzo, *pAp);
     const double beta = upd_p ? cg_ratio(*rz_new, rzo) : 0.0;
-    CGX_VEC_LOOP_BEGIN
-    d2 xv[kVU], pv[kVU], zv[kVU];
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            xv[u] = ldv<2>(x + i);
-            pv[u] = ldv<2>(p + i);
-            if (upd_p) zv[u] = ld2(z + i);
-        }
-#pragma unroll
-    for (int u = 0; u < kVU; ++u)
-        if (ok[u]) {
-            const int64_t i = 2 * (base + u * kNT);
-            d2 xn, pn;
-            xn.x = __builtin_fma(alpha, pv[u].x, xv[u].x);
-            xn.y = __builtin_fma(alpha, pv[u].y, xv[u].y);
-            stv<2>(x + i, xn);
-            if (upd_p) {
-                pn.x = __builtin_fma(beta, pv[u].x, zv[u].x);
-                pn.y = __builtin_fma(beta, pv[u].y, zv[u].y);
-                stv<2>(p + i, pn);
-            }
-        }
-    CGX_VEC_LOOP_END
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double pi = p[n - 1];
-        x[n - 1] = __builtin_fma(alpha, pi, x[n - 1]);
-        if (upd_p) p[n - 1] = __builtin_fma(beta, pi, z[n - 1]);
-    }
+    const auto body = [&](int64_t i, auto io, auto xv, auto pv, auto zv) {
+#pragma clang fp contract(off)
+        io.st(x + i, vfma(alpha, pv, xv));
+        if (upd_p) io.st(p + i, vfma(beta, pv, zv));
+    };
+    vec_pass<true, 2>(n, body, vin(x), vin(p), vopt<0>(z, upd_p));  // z: the r update's plain stores, read back plainly
 }
 
 // One-time set-up, one row per lane over the nblk * bs rows of the blocks:
@@ -316,12 +286,7 @@ hipError_t pcgb_update_xp_f64(int64_t n, double *x, double *p, const double *z, 
                               const double *pAp, const double *rr, const double *rz_new, hipStream_t s, double eps,
                               int64_t k, int64_t *kdone, double *rrfinal, int64_t *hrec) {
     if (!(al16(x) && al16(p) && al16(z))) return hipErrorInvalidValue;
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(k_pcgb_update_xp_f64, dim3(grid_vec(n)), dim3(kNT), 0, s, n, x, p, z, rz_old, pAp, rr, rz_new,
                        cv);
     return hipGetLastError();

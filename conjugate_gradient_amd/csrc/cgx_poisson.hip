@@ -921,12 +921,7 @@ hipError_t poisson_p_f64(const double *rh, const double *poh, double *pnh, int64
     if (!poisson_fusable(mloc, m) || !al16(rh) || !al16(pnh) || (!first && !al16(poh))) return hipErrorInvalidValue;
     if ((r_up && !al16(r_up)) || (r_dn && !al16(r_dn)) || (rr_sum && (rr_sum->cnt < 0 || rr_sum->cnt > kMaxPeers)))
         return hipErrorInvalidValue;
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     const PoissonPlan pl = poisson_plan(mloc, m);
     const int64_t nruns = pl.nitems / pl.nstrips, ns = pl.nstrips;
     // part 0: every item; 1: runs 1..nruns-2 (no halo row read); 2: runs 0 and

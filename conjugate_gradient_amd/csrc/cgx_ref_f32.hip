@@ -548,18 +548,12 @@ __global__ __launch_bounds__(kNT) void k_update_p_ref_f32(int64_t n, float *__re
                                                           const float *rr, const float *rsold, ConvArgs cv,
                                                           PeerSumF32 rr_sum) {
 #pragma clang fp contract(off)
-    if (cv.kdone) {
-        const int64_t kd = *cv.kdone;
-        if (kd != 0 && kd <= cv.k) return;
-    }
-    const float rrv = rr_sum.cnt ? peer_sum_mpich_f32(rr_sum) : *rr;
-    if (cv.kdone) {
-        const double rrn = (double)rrv;
-        if (cv.eps >= 0.0 && sqrt(rrn) < cv.eps) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) record_convergence(cv, cv.k + 1, rrn);
-            return;
-        }
-    }
+    float rrv = 0.0f;  // the float r.r itself; the decision takes it widened
+    const StopStep st = gated_stop(cv, true, [&] {
+        rrv = rr_sum.cnt ? peer_sum_mpich_f32(rr_sum) : *rr;
+        return (double)rrv;
+    });
+    if (!st.live || !st.upd_p) return;  // converged now or earlier: p stays (the loop has ended)
     const float ratio = rrv / *rsold;
     for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
         const float t = p[i] * ratio;
@@ -624,12 +618,7 @@ hipError_t update_xrp_dot_ref_f32(int64_t n, float *x, float *r, float *p, const
     d.Ap = Ap;
     d.rsold = rsold;
     d.pAp = pAp;
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(k_dot_ref_f32_blk<kDotXRP>, dim3(1), dim3(256), 0, s, n, d, rr, gate, cv);
     return hipGetLastError();
 }
@@ -686,12 +675,7 @@ hipError_t update_p_ref_f32(int64_t n, float *p, const float *r, const float *rr
         if (rr_sum->cnt < 0 || rr_sum->cnt > kMaxPeers) return hipErrorInvalidValue;
         rs = *rr_sum;
     }
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(k_update_p_ref_f32, dim3(grid_vec(n)), dim3(kNT), 0, s, n, p, r, rr, rsold, cv, rs);
     return hipGetLastError();
 }

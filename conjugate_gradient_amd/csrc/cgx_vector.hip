@@ -2,7 +2,13 @@
 // the x/r/p updates with the device-side stopping decision, dot), the
 // counter-hash SPD generator, fill and the rank-ordered scalar sum.
 // serialConjugate.c:122-177 (vecVec, scalarVec, vecAdd, vecSub) and :209-243.
-#include "cgx_device.h"
+//
+// Every element-wise kernel is one vec_pass (cgx_vector_core.h): the kernel
+// lists its streams and writes its element expression once; the pass runs it
+// on 16-byte pairs (VEC: every pointer 16-B aligned), on the odd last element
+// and in the scalar form.  Per-thread sums run in the pass's fixed order, then
+// the deterministic grid reduction.
+#include "cgx_vector_core.h"
 
 namespace cgx {
 namespace {
@@ -21,40 +27,35 @@ __global__ __launch_bounds__(kNT) void k_residual_f64(int64_t n, const double *_
                                                       unsigned *ticket, int64_t *clear2) {
     if (clear2 && blockIdx.x == 0 && threadIdx.x < 2) clear2[threadIdx.x] = 0;
     double acc = 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 bv[kVU], av[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) { const int64_t i = 2 * (base + u * kNT); bv[u] = ld2(b + i); av[u] = Ax ? ld2(Ax + i) : (d2)(0.0); }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                const d2 ri = bv[u] - av[u];
-                st2(r + i, ri);
-                if (p) st2(p + i, ri);
-                acc += ri.x * ri.x + ri.y * ri.y;
-            }
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const double ri = b[n - 1] - (Ax ? Ax[n - 1] : 0.0);
-            r[n - 1] = ri;
-            if (p) p[n - 1] = ri;
-            acc += ri * ri;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
-            const double ri = b[i] - (Ax ? Ax[i] : 0.0);
-            r[i] = ri;
-            if (p) p[i] = ri;
-            acc += ri * ri;
-        }
-    }
+    const auto body = [&](int64_t i, auto io, auto bv, auto av) {
+        const auto ri = bv - av;
+        io.st(r + i, ri);
+        if (p) io.st(p + i, ri);
+        acc += elem_dot(ri, ri);
+    };
+    vec_pass<VEC, 0>(n, body, vin(b), vopt(Ax, Ax != nullptr));
     if (rr_out) grid_sum_last_block(acc, partials, ticket, rr_out);
 }
 
-// x += alpha p; r -= alpha Ap; r.r  (serialConjugate.c:219-234, conjgrad.m:8-11)
+// x += alpha p; r -= alpha Ap, handed to store_r(io, i, r_i); returns the
+// thread's share of r.r  (serialConjugate.c:219-234, conjgrad.m:8-11).  The
+// one spelling behind k_update_xr_f64, k_update_xrp_f64 and
+// k_update_xr_stop_f64, which differ in load policy, in how r is stored and
+// in what follows the reduction: their x, r and r.r agree bit for bit.
+template <bool VEC, int VP, class SR>
+__device__ __forceinline__ double xr_pass(int64_t n, double *x, const double *r, const double *p, const double *Ap,
+                                          double alpha, SR store_r) {
+    double acc = 0.0;
+    const auto body = [&](int64_t i, auto io, auto xv, auto rv, auto pv, auto av) {
+        io.st(x + i, axpy_x(xv, alpha, pv));
+        const auto ri = sub_r(rv, alpha, av);
+        store_r(io, i, ri);
+        acc += elem_dot(ri, ri);
+    };
+    vec_pass<VEC, VP>(n, body, vin(x), vin(r), vin(p), vin(Ap));
+    return acc;
+}
+
 template <bool VEC, int VP = 0>
 __global__ __launch_bounds__(kNT) void k_update_xr_f64(int64_t n, double *__restrict__ x,
                                                        double *__restrict__ r,
@@ -64,41 +65,7 @@ __global__ __launch_bounds__(kNT) void k_update_xr_f64(int64_t n, double *__rest
                                                        double *rr_out, double *partials,
                                                        unsigned *ticket) {
     const double alpha = cg_ratio(*rsold, *pAp);
-    double acc = 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 xv[kVU], rv[kVU], pv[kVU], av[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                xv[u] = ldv<VP>(x + i); rv[u] = ldv<VP>(r + i); pv[u] = ldv<VP>(p + i); av[u] = ldv<VP>(Ap + i);
-            }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                stv<VP>(x + i, xv[u] + alpha * pv[u]);
-                const d2 ri = rv[u] - alpha * av[u];
-                stv<VP>(r + i, ri);
-                acc += ri.x * ri.x + ri.y * ri.y;
-            }
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const int64_t i = n - 1;
-            x[i] = x[i] + alpha * p[i];
-            const double ri = r[i] - alpha * Ap[i];
-            r[i] = ri;
-            acc += ri * ri;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
-            x[i] = x[i] + alpha * p[i];
-            const double ri = r[i] - alpha * Ap[i];
-            r[i] = ri;
-            acc += ri * ri;
-        }
-    }
+    const double acc = xr_pass<VEC, VP>(n, x, r, p, Ap, alpha, [&](auto io, int64_t i, auto ri) { io.st(r + i, ri); });
     grid_sum_last_block(acc, partials, ticket, rr_out);
 }
 
@@ -108,21 +75,8 @@ __global__ __launch_bounds__(kNT) void k_update_p_f64(int64_t n, double *__restr
                                                       const double *__restrict__ r,
                                                       const double *rr, const double *rsold) {
     const double beta = cg_ratio(*rr, *rsold);
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 pv[kVU], rv[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) { const int64_t i = 2 * (base + u * kNT); pv[u] = ldv<VP>(p + i); rv[u] = ldv<VP>(r + i); }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) stv<VP>(p + 2 * (base + u * kNT), rv[u] + beta * pv[u]);
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) p[n - 1] = r[n - 1] + beta * p[n - 1];
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT)
-            p[i] = r[i] + beta * p[i];
-    }
+    const auto body = [&](int64_t i, auto io, auto pv, auto rv) { io.st(p + i, next_p(rv, beta, pv)); };
+    vec_pass<VEC, VP>(n, body, vin(p), vin(r));
 }
 
 // The two-launch iteration (small systems, one GPU; cgx_iterate.hip): after
@@ -134,8 +88,8 @@ __global__ __launch_bounds__(kNT) void k_update_p_f64(int64_t n, double *__restr
 // -- the update kernel of the three-launch iteration folded into this one's
 // last block.  r crosses blocks inside the launch, so it is stored
 // write-through (sc1) and that block reads it with sc1 loads (Guideline 16's
-// one-counter row).  The expressions are the three-launch kernels' own, so
-// x, r, p and r.r come out bit for bit the same.
+// one-counter row).  The expressions are the three-launch kernels' own
+// (xr_pass, next_p), so x, r, p and r.r come out bit for bit the same.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t vec_rsrc(const double *p, int64_t n) {
     return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)(n * 8), 0x00020000);
 }
@@ -158,41 +112,11 @@ __global__ __launch_bounds__(kNT) void k_update_xrp_f64(int64_t n, double *__res
     const double rs = *rsold;
     const double alpha = cg_ratio(rs, *pAp);
     const __amdgpu_buffer_rsrc_t rrs = vec_rsrc(r, n);
-    double acc = 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 xv[kVU], rv[kVU], pv[kVU], av[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                xv[u] = ld2(x + i); rv[u] = ld2(r + i); pv[u] = ld2(p + i); av[u] = ld2(Ap + i);
-            }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                st2(x + i, xv[u] + alpha * pv[u]);
-                const d2 ri = rv[u] - alpha * av[u];
-                st2_sc1(rrs, i, ri);
-                acc += ri.x * ri.x + ri.y * ri.y;
-            }
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const int64_t i = n - 1;
-            x[i] = x[i] + alpha * p[i];
-            const double ri = r[i] - alpha * Ap[i];
-            __hip_atomic_store(r + i, ri, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc += ri * ri;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
-            x[i] = x[i] + alpha * p[i];
-            const double ri = r[i] - alpha * Ap[i];
-            __hip_atomic_store(r + i, ri, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc += ri * ri;
-        }
-    }
+    // r is stored write-through: 16-B sc1 buffer stores, 8-B agent-scope atomic stores
+    const double acc = xr_pass<VEC, 0>(n, x, r, p, Ap, alpha, [&](auto io, int64_t i, auto ri) {
+        if constexpr (decltype(io)::pair) st2_sc1(rrs, i, ri);
+        else __hip_atomic_store(r + i, ri, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's r stores land before the ticket
     double rr;
     if (!grid_sum_keep_last(acc, partials, ticket, rr_out, rr)) {
@@ -224,13 +148,13 @@ __global__ __launch_bounds__(kNT) void k_update_xrp_f64(int64_t n, double *__res
                 }
 #pragma unroll
             for (int u = 0; u < kPU; ++u)
-                if (b0 + u * kNT < npairs) st2(p + 2 * (b0 + u * kNT), rv[u] + beta * pv[u]);
+                if (b0 + u * kNT < npairs) st2(p + 2 * (b0 + u * kNT), next_p(rv[u], beta, pv[u]));
         }
         if ((n & 1) && threadIdx.x == 0)
-            p[n - 1] = __hip_atomic_load(r + n - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + beta * p[n - 1];
+            p[n - 1] = next_p(__hip_atomic_load(r + n - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), beta, p[n - 1]);
     } else {
         for (int64_t i = threadIdx.x; i < n; i += kNT)
-            p[i] = __hip_atomic_load(r + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + beta * p[i];
+            p[i] = next_p(__hip_atomic_load(r + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), beta, p[i]);
     }
     ts_end(ts);
 }
@@ -238,7 +162,7 @@ __global__ __launch_bounds__(kNT) void k_update_xrp_f64(int64_t n, double *__res
 // The update of the folded two-launch iteration (k_matvec_fold_f64 formed
 // p_k): x += alpha p_k; r -= alpha Ap; r.r, and the block that sums the r.r
 // partials decides the stop (serialConjugate.c:235).  Fully parallel: the
-// p update is the next matVec's.  The expressions are k_update_xrp_f64's.
+// p update is the next matVec's.  The pass is k_update_xrp_f64's (xr_pass).
 template <bool VEC>
 __global__ __launch_bounds__(kNT) void k_update_xr_stop_f64(int64_t n, double *__restrict__ x, double *__restrict__ r,
                                                             const double *__restrict__ p, const double *__restrict__ Ap,
@@ -248,41 +172,7 @@ __global__ __launch_bounds__(kNT) void k_update_xr_stop_f64(int64_t n, double *_
     if (gate && *gate) return;
     ts_start(ts);
     const double alpha = cg_ratio(*rsold, *pAp);
-    double acc = 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 xv[kVU], rv[kVU], pv[kVU], av[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                xv[u] = ld2(x + i); rv[u] = ld2(r + i); pv[u] = ld2(p + i); av[u] = ld2(Ap + i);
-            }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                st2(x + i, xv[u] + alpha * pv[u]);
-                const d2 ri = rv[u] - alpha * av[u];
-                st2(r + i, ri);
-                acc += ri.x * ri.x + ri.y * ri.y;
-            }
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const int64_t i = n - 1;
-            x[i] = x[i] + alpha * p[i];
-            const double ri = r[i] - alpha * Ap[i];
-            r[i] = ri;
-            acc += ri * ri;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
-            x[i] = x[i] + alpha * p[i];
-            const double ri = r[i] - alpha * Ap[i];
-            r[i] = ri;
-            acc += ri * ri;
-        }
-    }
+    const double acc = xr_pass<VEC, 0>(n, x, r, p, Ap, alpha, [&](auto io, int64_t i, auto ri) { io.st(r + i, ri); });
     double rr;
     if (grid_sum_keep_last(acc, partials, ticket, rr_out, rr) && cv.kdone && cv.eps >= 0.0 && sqrt(rr) < cv.eps &&
         threadIdx.x == 0)
@@ -302,32 +192,12 @@ __global__ __launch_bounds__(kNT) void k_update_r_f64(int64_t n, double *__restr
     ts_start(ts);
     const double alpha = cg_ratio(*rsold, pap_sum.cnt ? peer_sum_wave(pap_sum) : *pAp);
     double acc = 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 rv[kVU], av[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) { const int64_t i = 2 * (base + u * kNT); rv[u] = ldv<VP>(r + i); av[u] = ldv<VP>(Ap + i); }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const d2 ri = rv[u] - alpha * av[u];
-                stv<VP>(r + 2 * (base + u * kNT), ri);
-                acc += ri.x * ri.x + ri.y * ri.y;
-            }
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const double ri = r[n - 1] - alpha * Ap[n - 1];
-            r[n - 1] = ri;
-            acc += ri * ri;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
-            const double ri = r[i] - alpha * Ap[i];
-            r[i] = ri;
-            acc += ri * ri;
-        }
-    }
+    const auto body = [&](int64_t i, auto io, auto rv, auto av) {
+        const auto ri = sub_r(rv, alpha, av);
+        io.st(r + i, ri);
+        acc += elem_dot(ri, ri);
+    };
+    vec_pass<VEC, VP>(n, body, vin(r), vin(Ap));
     grid_sum_last_block(acc, partials, ticket, rr_out);
     ts_end(ts);
 }
@@ -343,49 +213,19 @@ __global__ __launch_bounds__(kNT) void k_update_xp_f64(int64_t n, double *__rest
                                                        const double *__restrict__ r, const double *rsold,
                                                        const double *pAp, const double *rr, ConvArgs cv,
                                                        int64_t *ts, PeerSum rr_sum) {
-    bool upd_p = rr != nullptr;
-    if (cv.kdone && *cv.kdone != 0 && *cv.kdone <= cv.k) return;
-    // the r.r combine folded in (multi-shard): every block sums the partials
-    const double rrv = rr_sum.cnt ? peer_sum_wave(rr_sum) : rr ? *rr : 0.0;
-    if (cv.kdone) {
-        const double rrn = rrv;
-        if (cv.eps >= 0.0 && sqrt(rrn) < cv.eps) {
-            upd_p = false;
-            if (blockIdx.x == 0 && threadIdx.x == 0) record_convergence(cv, cv.k + 1, rrn);
-        }
-    }
+    // r.r: the combine folded in (multi-shard: every block sums the partials), or *rr
+    const StopStep st =
+        gated_stop(cv, rr != nullptr, [&] { return rr_sum.cnt ? peer_sum_wave(rr_sum) : rr ? *rr : 0.0; });
+    if (!st.live) return;
+    const bool upd_p = st.upd_p;
     ts_start(ts);
     const double alpha = cg_ratio(*rsold, *pAp);
-    const double beta = upd_p ? cg_ratio(rrv, *rsold) : 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 xv[kVU], pv[kVU], rv[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                xv[u] = ldv<VP>(x + i);
-                pv[u] = ldv<VP>(p + i);
-                if (upd_p) rv[u] = ldv<VP>(r + i);
-            }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) {
-                const int64_t i = 2 * (base + u * kNT);
-                stv<VP>(x + i, xv[u] + alpha * pv[u]);
-                if (upd_p) stv<VP>(p + i, rv[u] + beta * pv[u]);
-            }
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            x[n - 1] = x[n - 1] + alpha * p[n - 1];
-            if (upd_p) p[n - 1] = r[n - 1] + beta * p[n - 1];
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT) {
-            x[i] = x[i] + alpha * p[i];
-            if (upd_p) p[i] = r[i] + beta * p[i];
-        }
-    }
+    const double beta = upd_p ? cg_ratio(st.rr, *rsold) : 0.0;
+    const auto body = [&](int64_t i, auto io, auto xv, auto pv, auto rv) {
+        io.st(x + i, axpy_x(xv, alpha, pv));
+        if (upd_p) io.st(p + i, next_p(rv, beta, pv));
+    };
+    vec_pass<VEC, VP>(n, body, vin(x), vin(p), vopt(r, upd_p));
     ts_end(ts);
 }
 
@@ -394,21 +234,8 @@ __global__ __launch_bounds__(kNT) void k_dot_f64(int64_t n, const double *__rest
                                                  const double *__restrict__ b, double *out,
                                                  double *partials, unsigned *ticket) {
     double acc = 0.0;
-    if constexpr (VEC) {
-        CGX_VEC_LOOP_BEGIN
-        d2 av[kVU], bv[kVU];
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) { const int64_t i = 2 * (base + u * kNT); av[u] = ld2(a + i); bv[u] = ld2(b + i); }
-#pragma unroll
-        for (int u = 0; u < kVU; ++u)
-            if (ok[u]) acc += av[u].x * bv[u].x + av[u].y * bv[u].y;
-        CGX_VEC_LOOP_END
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) acc += a[n - 1] * b[n - 1];
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kNT)
-            acc += a[i] * b[i];
-    }
+    const auto body = [&](int64_t, auto, auto av, auto bv) { acc += elem_dot(av, bv); };
+    vec_pass<VEC, 0>(n, body, vin(a), vin(b));
     grid_sum_last_block(acc, partials, ticket, out);
 }
 
@@ -657,12 +484,7 @@ hipError_t update_xrp_f64(int64_t n, double *x, double *r, double *p, const doub
                           double eps, int64_t k, int64_t *kdone, double *rrfinal, int64_t *hrec, int64_t *ts) {
     if (n * 8 > INT32_MAX) return hipErrorInvalidValue;  // buffer-resource offsets are 32-bit
     const bool vec = al16(x) && al16(r) && al16(p) && al16(Ap);
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(vec ? k_update_xrp_f64<true> : k_update_xrp_f64<false>, dim3(grid_vec(n)), dim3(kNT), 0, s,
                        n, x, r, p, Ap, rsold, pAp, rr_out, ws.partials, ws.tickets + T_XR, gate, cv, ts);
     return hipGetLastError();
@@ -673,12 +495,7 @@ hipError_t update_xr_stop_f64(int64_t n, double *x, double *r, const double *p, 
                               const int64_t *gate, double eps, int64_t k, int64_t *kdone, double *rrfinal,
                               int64_t *hrec, int64_t *ts) {
     const bool vec = al16(x) && al16(r) && al16(p) && al16(Ap);
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(vec ? k_update_xr_stop_f64<true> : k_update_xr_stop_f64<false>, dim3(grid_vec(n)), dim3(kNT),
                        0, s, n, x, r, p, Ap, rsold, pAp, rr_out, ws.partials, ws.tickets + T_XR, gate, cv, ts);
     return hipGetLastError();
@@ -690,12 +507,7 @@ hipError_t update_xp_f64(int64_t n, double *x, double *p, const double *r, const
     const bool vec = al16(x) && al16(p) && al16(r);
     PeerSum ps{};
     if (rr_sum) ps = *rr_sum;
-    ConvArgs cv;
-    cv.eps = eps;
-    cv.k = k;
-    cv.kdone = kdone;
-    cv.rrfinal = rrfinal;
-    cv.hrec = hrec;
+    const ConvArgs cv = conv_args(eps, k, kdone, rrfinal, hrec);
     hipLaunchKernelGGL(vec ? k_update_xp_f64<true> : k_update_xp_f64<false>, dim3(grid_vec(n)), dim3(kNT), 0, s, n, x,
                        p, r, rsold, pAp, rr, cv, ts, ps);
     return hipGetLastError();
