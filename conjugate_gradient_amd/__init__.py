@@ -39,6 +39,7 @@ __all__ = [
     "device_pci_bus_id", "device_link",
     "CGX_MAX_NRHS", "matVec_nrhs",
     "CGX_CSR_ACTIVE", "spmv_csr", "spmm_csr",
+    "CGX_BSR_ACTIVE", "CGX_MAX_BSR_BLOCK", "bsr_check", "spmv_bsr",
     "CGX_CSR_HALO_ACTIVE", "csr_halo_counts", "csr_halo_list", "gather_indexed",
     "CGX_PRECOND_ACTIVE", "PRECOND_KINDS", "PC_BLOCK", "CGX_MAX_PC_BLOCK", "csr_diag_blocks", "precond_block_invert",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
@@ -71,6 +72,8 @@ CGX_CSR_ACTIVE = 0x8000000  # reported in info.flags: a cgx_create_csr context (
 CGX_PRECOND_ACTIVE = 0x10000000  # reported in info.flags: a CSR context iterating with a diagonal preconditioner
 # reported in info.flags: a CSR solver over several row blocks (devices=) exchanging p by index lists
 CGX_CSR_HALO_ACTIVE = 0x20000000
+CGX_BSR_ACTIVE = 0x40000000  # reported in info.flags beside CGX_CSR_ACTIVE: a CSR solver that is block-valued (set_bsr)
+CGX_MAX_BSR_BLOCK = 8  # the largest block size of set_bsr
 # cgx_set_precond's kinds, CGX_PC_NONE / CGX_PC_JACOBI / CGX_PC_DIAG (include/cgx.h), by the names Solver.precond
 # reports.  Kept out of the CGX_* names: those are the flag words, and a kind is not a bit of one.
 PRECOND_KINDS = {"none": 0, "jacobi": 1, "diag": 2}
@@ -190,6 +193,10 @@ def lib() -> ctypes.CDLL:
         "cgx_set_csr": ([vp, vp, vp, vp], i32),
         "cgx_set_csr_f32": ([vp, vp, vp, vp], i32),
         "cgx_spmv_csr": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
+        "cgx_bsr_check": ([i64, i64, vp, vp], i32),
+        "cgx_set_bsr": ([vp, i32, vp, vp, vp], i32),
+        "cgx_bsr_tile_values": ([i64, i32, vp, vp, vp], i32),
+        "cgx_spmv_bsr": ([i64, i64, i32, vp, vp, vp, vp, vp, vp], i32),
         "cgx_spmv_csr_f32": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_create_csr_nrhs": ([pctx, i64, i64, i32, i32, i32], i32),
         "cgx_create_csr_multi": ([pctx, i64, i64, i32, ctypes.POINTER(i32), i32], i32),
@@ -455,12 +462,17 @@ def _csr_arrays(indptr, indices=None, data=None, a_f32: bool = False):
 
 def _csr_checked(what: str, rp, ci, rows: int, cols: int) -> None:
     """The structure check of the kernel-level CSR calls: raises unless every index is inside [0, cols)."""
+    _csr_checked_with(lib().cgx_csr_check, "cgx_csr_check", what, rp, ci, rows, cols)
+
+
+def _csr_checked_with(check, check_name: str, what: str, rp, ci, rows: int, cols: int) -> None:
+    """_csr_checked through `check` (cgx_csr_check, or cgx_bsr_check on block rows and block columns)."""
     # cgx_csr_check takes a square structure: fewer rows than columns are
     # padded with empty rows (the same last row pointer), so the columns are
     # checked against cols; with more rows than columns they are checked here
     nsq = max(rows, cols)
     rp_sq = rp if nsq == rows else np.concatenate([rp, np.full(nsq - rows, rp[-1], np.int64)])
-    _check(lib().cgx_csr_check(nsq, ci.size, _ptr(rp_sq), _ptr(ci)), "cgx_csr_check")
+    _check(check(nsq, ci.size, _ptr(rp_sq), _ptr(ci)), check_name)
     bad = np.flatnonzero(ci >= cols)
     _need(bad.size == 0, f"{what}: indices[{bad[0] if bad.size else 0}] outside [0, {cols})")
 
@@ -519,6 +531,72 @@ def spmm_csr(indptr, indices, data, V: DeviceArray, Out: DeviceArray, rows: int,
         _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
     finally:
         for d in (d_rp, d_ci, d_va):
+            d.free()
+
+
+def _bsr_arrays(what: str, indptr, indices=None, data=None):
+    """(indptr int64, indices int32, data float64 of shape (nnzb, bs, bs), bs), contiguous; ``indptr`` may be an
+    object with ``.indptr / .indices / .data`` such as scipy's bsr_matrix (no scipy needed).  Raises unless the
+    blocks are square with 2 <= bs <= CGX_MAX_BSR_BLOCK."""
+    if indices is None and data is None and hasattr(indptr, "indptr"):
+        indptr, indices, data = indptr.indptr, indptr.indices, indptr.data
+    _need(indices is not None and data is not None, f"{what}: indptr, indices and data are needed")
+    d = np.asarray(data)
+    _need(d.dtype.kind in "fiu", f"{what}: data must be real numbers (got {d.dtype})")
+    rp = np.ascontiguousarray(indptr, np.int64)
+    ci = np.ascontiguousarray(indices, np.int32)
+    va = np.ascontiguousarray(d, np.float64)
+    _need(rp.ndim == 1 and ci.ndim == 1, f"{what}: indptr and indices are one-dimensional")
+    _need(va.ndim == 3 and va.shape[1] == va.shape[2],
+          f"{what}: data must have shape (nnzb, bs, bs) (got {va.shape})")
+    bs = int(va.shape[1])
+    _need(bs != 1, f"{what}: bs = 1 is scalar CSR (set_csr / spmv_csr)")
+    _need(2 <= bs <= CGX_MAX_BSR_BLOCK, f"{what}: bs must be in [2, {CGX_MAX_BSR_BLOCK}] (got {bs})")
+    _need(ci.size == va.shape[0], f"{what}: {ci.size} indices but {va.shape[0]} blocks")
+    return rp, ci, va, bs
+
+
+def bsr_check(indptr, indices, nb: int | None = None) -> None:
+    """cgx_bsr_check (host only, no GPU): raises CgxError(-4) naming the first offence of a block structure of
+    ``nb`` block rows and ``nb`` block columns (default: ``len(indptr) - 1``)."""
+    rp = np.ascontiguousarray(indptr, np.int64)
+    ci = np.ascontiguousarray(indices, np.int32)
+    _need(rp.ndim == 1 and ci.ndim == 1, "bsr_check: indptr and indices are one-dimensional")
+    nb = rp.size - 1 if nb is None else nb
+    _need(isinstance(nb, (int, np.integer)) and rp.size == nb + 1,
+          f"bsr_check: indptr has {rp.size} entries, nb + 1 = {nb + 1 if isinstance(nb, (int, np.integer)) else nb} needed")
+    _check(lib().cgx_bsr_check(int(nb), ci.size, _ptr(rp), _ptr(ci)), "cgx_bsr_check")
+
+
+def spmv_bsr(indptr, indices, data, v: DeviceArray, out: DeviceArray, nb: int, ncolb: int) -> None:
+    """out[I bs + i] = sum over block row I's blocks q, in stored order, and j ascending of
+    data[q, i, j] * v[indices[q] bs + j] (k_bsr_mult_f64; the plan from CGX_BSMV_PLAN).  ``data`` has shape
+    (nnzb, bs, bs).  The structure comes as host arrays: it is checked (cgx_bsr_check) and only then uploaded, so
+    the kernel never sees a block column outside v; the values are re-laid on the device (cgx_bsr_tile_values),
+    then multiplied (cgx_spmv_bsr)."""
+    rp, ci, va, bs = _bsr_arrays("spmv_bsr", indptr, indices, data)
+    _need(isinstance(nb, (int, np.integer)) and isinstance(ncolb, (int, np.integer)) and nb >= 1 and ncolb >= 1,
+          "spmv_bsr: need integers nb, ncolb >= 1")
+    _need(rp.size == nb + 1, f"spmv_bsr: indptr has {rp.size} entries, nb + 1 = {nb + 1} needed")
+    _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_bsr: float64 only")
+    _fits([v], ncolb * bs, "spmv_bsr v")
+    _fits([out], nb * bs, "spmv_bsr out")
+    L = lib()
+    # cgx_bsr_check takes a square block structure: fewer block rows than block columns are padded with empty
+    # block rows, so the block columns are checked against ncolb; with more rows than columns they are checked here
+    _csr_checked_with(L.cgx_bsr_check, "cgx_bsr_check", "spmv_bsr", rp, ci, nb, ncolb)
+    if ci.size == 0:  # nothing to re-lay: one pad tile, so the pointers are real
+        va = np.zeros((1, bs, bs))
+    nnzb = int(ci.size)
+    d_rp, d_ci = DeviceArray.from_host(rp), DeviceArray.from_host(ci if nnzb else np.zeros(1, np.int32))
+    d_va, d_t = DeviceArray.from_host(va.reshape(-1)), DeviceArray((max(nnzb, 1) + 63) // 64 * 64 * bs * bs)
+    try:
+        _check(L.cgx_bsr_tile_values(nnzb, bs, d_va.ptr, d_t.ptr, None), "cgx_bsr_tile_values")
+        _check(L.cgx_spmv_bsr(int(nb), int(ncolb), bs, d_rp.ptr, d_ci.ptr, d_t.ptr, v.ptr, out.ptr, None),
+               "cgx_spmv_bsr")
+        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
+    finally:
+        for d in (d_rp, d_ci, d_va, d_t):
             d.free()
 
 
@@ -827,6 +905,44 @@ class Solver:
             _check(lib().cgx_set_csr_f32(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr_f32")
         else:
             _check(lib().cgx_set_csr(self._h, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_csr")
+
+    @classmethod
+    def from_bsr(cls, indptr, indices=None, data=None, *, precond=None, device: int = 0,
+                 flags: int = CGX_F64) -> "Solver":
+        """A CSR solver sized for this block matrix (room for nnzb * bs * bs entries), with the matrix set through
+        :meth:`set_bsr` (b = 0, x0 = 0) and, with ``precond`` ("jacobi", an array or ``("block", pbs)``), its
+        preconditioner (:meth:`set_precond`).  ``data`` has shape (nnzb, bs, bs); or pass one object with
+        ``.indptr / .indices / .data`` such as scipy's bsr_matrix."""
+        rp, ci, va, bs = _bsr_arrays("from_bsr", indptr, indices, data)
+        _need(rp.size >= 2, "from_bsr: indptr needs nb + 1 >= 2 entries")
+        s = cls.csr((rp.size - 1) * bs, int(ci.size) * bs * bs, device=device, flags=flags)
+        try:
+            s.set_bsr(rp, ci, va)
+            if precond is not None:
+                s.set_precond(precond)
+        except Exception:
+            s.close()
+            raise
+        return s
+
+    def set_bsr(self, indptr, indices=None, data=None) -> None:
+        """cgx_set_bsr: the matrix of a ``csr_nnz`` solver as dense ``bs x bs`` blocks, scipy's bsr_matrix layout
+        (``data`` of shape (nnzb, bs, bs), 2 <= bs <= 8, n = nb bs; or one object with
+        ``.indptr / .indices / .data``), multiplied by the block kernel k_bsr_mult_f64.  The structure is checked
+        before anything is uploaded: CgxError(-4) names the first offence and the earlier matrix stays.  The solver
+        is block-valued (``info().flags`` carries CGX_BSR_ACTIVE) until the next :meth:`set_csr`; preconditioning
+        is off afterwards, as after ``set_csr``.  One GPU, one right-hand side, float64 values."""
+        _need(getattr(self, "csr_nnz", None) is not None, "set_bsr: the solver was not created with csr_nnz=")
+        _need(getattr(self, "devices", None) is None and getattr(self, "nrhs", None) is None,
+              "set_bsr: block storage runs on one GPU with one right-hand side (not with devices= or nrhs=)")
+        rp, ci, va, bs = _bsr_arrays("set_bsr", indptr, indices, data)
+        _need(self.n % bs == 0, f"set_bsr: n = {self.n} is not divisible by bs = {bs}")
+        nb = self.n // bs
+        _need(rp.size == nb + 1, f"set_bsr: indptr has {rp.size} entries, n / bs + 1 = {nb + 1} needed")
+        _need(ci.size * bs * bs <= self.csr_nnz,
+              f"set_bsr: {ci.size} blocks of {bs} x {bs} are {ci.size * bs * bs} entries, the solver has room for "
+              f"{self.csr_nnz}")
+        _check(lib().cgx_set_bsr(self._h, bs, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_bsr")
 
     def csr_halo(self) -> np.ndarray:
         """cgx_get_csr_halo: the ``(nshards, nshards)`` exchange counts in use on a CSR solver over row blocks

@@ -48,7 +48,11 @@
  * reference's fscanf("%f") holds, on the host and on the GPU: cgx_set_csr_f32,
  * 8 bytes per entry streamed in place of 12, all arithmetic still fp64 on the
  * exactly widened values; takes --jacobi or --block-jacobi BS as --csr does and
- * is given without --csr; --stats adds "values: float").
+ * is given without --csr; --stats adds "values: float"),
+ * --bsr BS (with --csr, 2 <= BS <= 8 dividing N: every BS x BS block of the
+ * matrix that holds an entry is kept whole, zero-filled, and the solve runs
+ * through cgx_set_bsr and the block kernel; takes --jacobi or --block-jacobi
+ * as --csr does, not --csr-a32; --stats adds "nnzb: <count>").
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -134,8 +138,10 @@ static void usage(const char *prog) {
             "          as a sparse CSR system; --jacobi: preconditioned with 1 / diag(A); --block-jacobi BS: with the\n"
             "          inverses of A's BS x BS diagonal blocks, BS in 2..8)\n"
             "       %s --csr-a32 [--jacobi | --block-jacobi BS] ... (--csr with the values parsed and kept as float, fp64\n"
-            "          arithmetic; given without --csr)\n",
-            prog, prog, prog, prog, prog);
+            "          arithmetic; given without --csr)\n"
+            "       %s --csr --bsr BS [--jacobi | --block-jacobi BS] ... (--csr held as dense BS x BS blocks, BS in 2..8\n"
+            "          dividing N, multiplied by the block kernel; not with --csr-a32)\n",
+            prog, prog, prog, prog, prog, prog);
 }
 
 static int die_cgx(int rc, const char *what) {
@@ -329,6 +335,61 @@ static int csr_parse(cgx_text *text, int64_t n, int64_t block_rows, void *blk, i
     return 0;
 }
 
+/* --bsr BS: the CSR arrays of csr_parse as block CSR -- every BS x BS block
+ * that holds an entry, block columns ascending, the rest of a block +0.0
+ * (n % bs == 0, values double).  Returns 0, or -9 when memory runs out. */
+typedef struct {
+    int64_t *brow_ptr;
+    int32_t *bcol_idx;
+    double *values;
+    int64_t nnzb;
+} bsr_host;
+
+static int bsr_from_csr(const csr_host *m, int64_t n, int bs, bsr_host *out) {
+    const int64_t nb = n / bs;
+    const double *val = (const double *)m->values;
+    out->brow_ptr = malloc((size_t)(nb + 1) * sizeof(int64_t));
+    int64_t *slot = malloc((size_t)nb * sizeof(int64_t)); /* a block column's place in the current block row, or -1 */
+    if (!out->brow_ptr || !slot) { free(slot); return -9; }
+    for (int64_t c = 0; c < nb; ++c) slot[c] = -1;
+    /* pass 1 counts the blocks of every block row, pass 2 places them */
+    for (int pass = 0; pass < 2; ++pass) {
+        int64_t nnzb = 0;
+        for (int64_t I = 0; I < nb; ++I) {
+            /* the block columns the bs rows name, ascending: mark, then sweep between the lowest and the highest */
+            int64_t lo = nb, hi = -1;
+            for (int64_t e = m->row_ptr[I * bs]; e < m->row_ptr[(I + 1) * bs]; ++e) {
+                const int64_t c = m->col_idx[e] / bs;
+                slot[c] = -2;
+                if (c < lo) lo = c;
+                if (c > hi) hi = c;
+            }
+            for (int64_t c = lo; c <= hi; ++c)
+                if (slot[c] == -2) {
+                    if (pass) out->bcol_idx[nnzb] = (int32_t)c;
+                    slot[c] = nnzb++;
+                }
+            if (pass)
+                for (int i = 0; i < bs; ++i)
+                    for (int64_t e = m->row_ptr[I * bs + i]; e < m->row_ptr[I * bs + i + 1]; ++e) {
+                        const int64_t c = m->col_idx[e] / bs;
+                        out->values[(slot[c] * bs + i) * bs + (m->col_idx[e] - c * bs)] = val[e];
+                    }
+            for (int64_t c = lo; c <= hi; ++c) slot[c] = -1;
+            if (!pass) out->brow_ptr[I + 1] = nnzb;
+        }
+        if (!pass) {
+            out->brow_ptr[0] = 0;
+            out->nnzb = nnzb;
+            out->bcol_idx = malloc((size_t)(nnzb > 0 ? nnzb : 1) * sizeof(int32_t));
+            out->values = calloc((size_t)(nnzb > 0 ? nnzb : 1) * (size_t)(bs * bs), sizeof(double));
+            if (!out->bcol_idx || !out->values) { free(slot); return -9; }
+        }
+    }
+    free(slot);
+    return 0;
+}
+
 /* Whole-string numeric option values: "--eps abc" or "--gpus 2x" is an
  * error (exit 2), not a silent 0. */
 static int opt_ll(const char *name, const char *v, long long *out) {
@@ -356,6 +417,7 @@ int main(int argc, char **argv) {
     int threads = (int)(ncpu < 1 ? 1 : (ncpu > 16 ? 16 : ncpu)); /* text parsing threads */
     double eps = EPSILON_DEFAULT;
     long long max_iter = -1, n_opt = -1, spd_n = -1, nrhs = 0, block_bs = 0; /* block_bs > 0: --block-jacobi */
+    long long bsr_bs = 0; /* > 0: --bsr */
     unsigned long long seed = 42;
     const char *dims_path = NULL;
     const char *pos[3];
@@ -379,6 +441,12 @@ int main(int argc, char **argv) {
             if (has_val && !opt_ll(a, argv[++i], &block_bs)) return 2;
             if (!has_val || block_bs < 2 || block_bs > CGX_MAX_PC_BLOCK) {
                 fprintf(stderr, "--block-jacobi must be an integer in [2, %d]\n", CGX_MAX_PC_BLOCK);
+                return 2;
+            }
+        } else if (!strcmp(a, "--bsr")) {
+            if (has_val && !opt_ll(a, argv[++i], &bsr_bs)) return 2;
+            if (!has_val || bsr_bs < 2 || bsr_bs > CGX_MAX_BSR_BLOCK) {
+                fprintf(stderr, "--bsr must be an integer in [2, %d]\n", CGX_MAX_BSR_BLOCK);
                 return 2;
             }
         } else if (!strcmp(a, "--eps") && has_val) {
@@ -415,6 +483,10 @@ int main(int argc, char **argv) {
     if (gpus > 32) { fprintf(stderr, "--gpus must be <= 32\n"); return 2; }
     if (csr_a32 && (csr || fp32ref || a_fp32 || symmetric || gpus != 1 || p2p || nrhs > 0 || spd_n >= 0)) {
         fprintf(stderr, "--csr-a32 is --csr with float-stored values: it is given alone (no --csr, --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
+        return 2;
+    }
+    if (bsr_bs > 0 && (csr_a32 || !csr)) {
+        fprintf(stderr, "--bsr holds a --csr matrix as dense blocks of double values: it is given with --csr (not --csr-a32)\n");
         return 2;
     }
     if (csr_a32) csr = 1;
@@ -470,6 +542,10 @@ int main(int argc, char **argv) {
     }
     if (n < 1) { fprintf(stderr, "empty system\n"); return 1; }
     if (csr && n > INT32_MAX) { fprintf(stderr, "--csr: n must be below 2^31\n"); return 1; }
+    if (bsr_bs > 0 && n % bsr_bs != 0) {
+        fprintf(stderr, "--bsr %lld: n = %lld is not divisible by the block size\n", bsr_bs, (long long)n);
+        return 2;
+    }
     if (n % gpus != 0) { printf("%lld is not divisible by %d\n", (long long)n, gpus); return 1; } /* parallel_cg.c:88 */
 
     printf("Computing cg of matrix size : %lld\n", (long long)n * (long long)n); /* serialConjugate.c:58 */
@@ -520,6 +596,7 @@ int main(int argc, char **argv) {
     }
     create_job job = {n, gpus, flags, CGX_OK, (int)nrhs, NULL, 0.0, 0.0, csr, -1};
     csr_host csrm = {NULL, NULL, NULL, 0, 0};
+    bsr_host bsrm = {NULL, NULL, NULL, 0};
     const double t_start = now_s();
     pthread_t creator;
     const int threaded = pthread_create(&creator, NULL, create_ctx, &job) == 0;
@@ -559,6 +636,10 @@ int main(int argc, char **argv) {
                                   (long long)(n * n));
             read_rc = prc;
             rel.buf = Abuf;
+            if (!read_rc && bsr_bs > 0 && bsr_from_csr(&csrm, n, (int)bsr_bs, &bsrm) != 0) {
+                fprintf(stderr, "can't allocate memory for vector\n");
+                read_rc = -9;
+            }
         }
         t_parsed = now_s();
         if (threaded) pthread_join(creator, NULL); /* before any exit: HIP may be starting up on it */
@@ -566,7 +647,7 @@ int main(int argc, char **argv) {
             read_rc = read_file(pos[1], (int64_t)vlen, 0, b, threads) || read_file(pos[2], (int64_t)vlen, 0, x, 1);
         rel.text = text;
         if (!read_rc) {
-            job.csr_nnz = csrm.nnz;
+            job.csr_nnz = bsr_bs > 0 ? bsrm.nnzb * bsr_bs * bsr_bs : csrm.nnz; /* blocks are stored whole */
             create_ctx(&job);
         }
     } else if (stream_a) {
@@ -665,9 +746,10 @@ int main(int argc, char **argv) {
         t_dist1 = now_s();
         if (rc != CGX_OK) return die_cgx(rc, "cgx_generate_spd");
     } else if (csr) {
-        rc = csr_a32 ? cgx_set_csr_f32(ctx, csrm.row_ptr, csrm.col_idx, (const float *)csrm.values)
-                     : cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, (const double *)csrm.values);
-        if (rc != CGX_OK) return die_cgx(rc, csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
+        rc = bsr_bs > 0 ? cgx_set_bsr(ctx, (int)bsr_bs, bsrm.brow_ptr, bsrm.bcol_idx, bsrm.values)
+             : csr_a32  ? cgx_set_csr_f32(ctx, csrm.row_ptr, csrm.col_idx, (const float *)csrm.values)
+                        : cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, (const double *)csrm.values);
+        if (rc != CGX_OK) return die_cgx(rc, bsr_bs > 0 ? "cgx_set_bsr" : csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
         if (jacobi) { /* 1 / diag(A) from the uploaded matrix; a diagonal it refuses ends the run */
             rc = cgx_set_precond(ctx, CGX_PC_JACOBI);
             if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond");
@@ -682,6 +764,9 @@ int main(int argc, char **argv) {
         free(csrm.row_ptr);
         free(csrm.col_idx);
         free(csrm.values);
+        free(bsrm.brow_ptr);
+        free(bsrm.bcol_idx);
+        free(bsrm.values);
         if (rc != CGX_OK) return die_cgx(rc, "cgx_set_rows");
     } else if (stream_a) {
         /* A is on the device; b and x0 (MPI_Bcast / MPI_Scatter of the vectors) */
@@ -729,6 +814,7 @@ int main(int argc, char **argv) {
         printf("iterations: %lld converged: %d residual_norm: %.6e\n", (long long)st.iterations, st.converged,
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
     if (stats && csr) printf("nnz: %lld\n", (long long)csrm.nnz);
+    if (stats && bsr_bs > 0) printf("nnzb: %lld\n", (long long)bsrm.nnzb);
     if (stats && csr_a32) printf("values: float\n");
     if (stats && jacobi) printf("precond: jacobi\n");
     if (stats && block_bs > 0) printf("precond: block-jacobi %lld\n", block_bs);

@@ -20,6 +20,14 @@
 // on the host by cgx_pcblock.hip, or the caller's), and one more n-vector z;
 // the iteration then runs cgx_pcg_block.hip's kernels.
 //
+// cgx_set_bsr makes a plain cgx_create_csr context block-valued: brow_ptr and
+// bcol_idx take the places of row_ptr and col_idx, the values go up in the
+// host layout (what the preconditioners' extraction kernels read) and once more,
+// re-laid by k_bsr_tile_f64, into the library's own tiled buffer, which is what
+// k_bsr_mult_f64 multiplies (cgx_bsmv.hip).  Only launch_matvec, the plan and
+// the two extractions know the difference; the next cgx_set_csr /
+// cgx_set_csr_f32 makes the context a scalar one again.
+//
 // cgx_create_csr_multi (cgx_setup.hip) puts the matrix on several row blocks of
 // one process: cgx_set_csr splits the host arrays by rows (csr_upload_blocks)
 // and builds, per block, the lists of the entries of p it needs from every
@@ -49,8 +57,11 @@ int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
     TRY(csr_plan_args(1, R, U, nt));
     for (auto &s : c->sh) {  // one T for every row block, each block's grid from its own rows
         TRY(set_dev(s));
-        s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt, blocks_per_cu,
-                               c->csr_f32);
+        if (c->bsr_bs)  // block-valued: T lanes per block row
+            s.plan = plan_spmv_bsr(s.dev, s.nloc / c->bsr_bs, c->bsr_nnzb, c->bsr_bs, 64 / R, nt, blocks_per_cu);
+        else
+            s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt,
+                                   blocks_per_cu, c->csr_f32);
     }
     c->csr_plan_user = true;
     return CGX_OK;
@@ -167,9 +178,16 @@ static int pc_jacobi(cgx_ctx *c) {
         unsigned long long *pin = reinterpret_cast<unsigned long long *>(s.h_pin);
         pin[0] = ~0ull;
         HIPT(hipMemcpyAsync(slot(s, S_PCBAD), pin, 8, hipMemcpyHostToDevice, s.stream));
-        HIPT(csr_diag_minv_f64(c->n, reinterpret_cast<const int64_t *>(s.csr_rp),
-                               reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(fresh),
-                               static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
+        if (c->bsr_bs) {
+            HIPT(preload_kernels(PL_BSMV));
+            HIPT(bsr_diag_minv_f64(c->n, c->bsr_bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                   reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(fresh),
+                                   static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
+        } else {
+            HIPT(csr_diag_minv_f64(c->n, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                   reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(fresh),
+                                   static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
+        }
         HIPT(hipMemcpyAsync(pin, slot(s, S_PCBAD), 8, hipMemcpyDeviceToHost, s.stream));
         HIPT(hipStreamSynchronize(s.stream));
         const unsigned long long bad = pin[0];
@@ -370,11 +388,91 @@ static int csr_upload(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx
     HIPT(hipStreamSynchronize(s.stream));
     c->csr_nnz = nnz;
     c->csr_f32 = f32;
+    const bool was_bsr = c->bsr_bs != 0;  // block-valued until now: a scalar context again (the tiled buffer stays)
+    c->bsr_bs = 0;
+    c->bsr_nnzb = 0;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
     if (!c->csr_plan_user) {
         if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs), 0, -1, 0, f32);
         else s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 0, -1, 0, f32);
+    } else if (was_bsr) {  // the caller's T and policy, on scalar rows again
+        s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 64 / s.plan.R, s.plan.nt, 0, f32);
     }
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
+// What cgx_csr_check and cgx_bsr_check test, under the caller's names.
+struct StructureNames {
+    const char *fn, *n, *nnz, *rp, *ci, *row;
+};
+static int structure_check(const StructureNames &w, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                           const int32_t *col_idx) {
+    if (n < 1 || nnz < 0) return fail(CGX_ERR_ARG, "%s: %s must be >= 1 and %s >= 0", w.fn, w.n, w.nnz);
+    if (!row_ptr || (nnz > 0 && !col_idx)) return fail(CGX_ERR_ARG, "%s: NULL pointer", w.fn);
+    if (row_ptr[0] != 0)
+        return fail(CGX_ERR_SHAPE, "%s: %s[0] = %lld, must be 0", w.fn, w.rp, (long long)row_ptr[0]);
+    for (int64_t i = 0; i < n; ++i)
+        if (row_ptr[i + 1] < row_ptr[i])
+            return fail(CGX_ERR_SHAPE, "%s: %s decreases at %s %lld (%lld -> %lld)", w.fn, w.rp, w.row, (long long)i,
+                        (long long)row_ptr[i], (long long)row_ptr[i + 1]);
+    if (row_ptr[n] != nnz)
+        return fail(CGX_ERR_SHAPE, "%s: %s[%s] = %lld, must be %s = %lld", w.fn, w.rp, w.n, (long long)row_ptr[n],
+                    w.nnz, (long long)nnz);
+    for (int64_t e = 0; e < nnz; ++e)
+        if (col_idx[e] < 0 || (int64_t)col_idx[e] >= n)
+            return fail(CGX_ERR_SHAPE, "%s: %s[%lld] = %d outside [0, %lld)", w.fn, w.ci, (long long)e,
+                        (int)col_idx[e], (long long)n);
+    return CGX_OK;
+}
+
+// cgx_set_bsr, after its checks: the arrays go up, the values once in the host
+// layout and once re-laid for the kernel.  A tiled buffer that has to grow is
+// allocated before the first byte moves, so a refusal leaves the earlier matrix.
+static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr, const int32_t *bcol_idx,
+                      const double *values) {
+    Shard &s = c->sh[0];
+    const int64_t nb = c->n / bs, need = bsr_tiled_count(nnzb, bs);
+    TRY(sync_all(c));  // iterations still enqueued read the arrays
+    TRY(set_dev(s));
+    HIPT(preload_kernels(PL_BSMV));
+    char *fresh = nullptr;
+    if (need > s.bsr_cap) {
+        const hipError_t e = hipMalloc(&fresh, (size_t)need * 8);
+        if (e != hipSuccess)
+            return fail(CGX_ERR_NOMEM, "hipMalloc(%zu bytes) on device %d: %s", (size_t)need * 8, s.dev,
+                        hipGetErrorString(e));
+    }
+    char *tiled = fresh ? fresh : s.bsr_val;
+    const int rc = [&]() -> int {
+        HIPT(hipMemcpyAsync(s.csr_rp, brow_ptr, (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, s.stream));
+        if (nnzb > 0) {
+            HIPT(hipMemcpyAsync(s.csr_ci, bcol_idx, (size_t)nnzb * 4, hipMemcpyHostToDevice, s.stream));
+            HIPT(hipMemcpyAsync(s.csr_val, values, (size_t)nnzb * bs * bs * 8, hipMemcpyHostToDevice, s.stream));
+            HIPT(bsr_tile_values_f64(nnzb, bs, f64(s.csr_val), f64(tiled), s.stream));
+        }
+        HIPT(hipStreamSynchronize(s.stream));
+        return CGX_OK;
+    }();
+    if (rc != CGX_OK) {  // part of the new matrix is on the device: no matrix until the next cgx_set_csr / cgx_set_bsr
+        if (fresh) (void)hipFree(fresh);
+        c->csr_nnz = -1;
+        c->bsr_bs = 0;
+        c->state = ST_IDLE;
+        return rc;
+    }
+    if (fresh) {
+        if (s.bsr_val) HIPT(hipFree(s.bsr_val));
+        s.bsr_val = fresh;
+        s.bsr_cap = need;
+    }
+    c->csr_nnz = nnzb * bs * bs;
+    c->csr_f32 = false;
+    c->bsr_bs = bs;
+    c->bsr_nnzb = nnzb;
+    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
+    if (!c->csr_plan_user) s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs);
+    else s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs, 64 / s.plan.R, s.plan.nt);  // the caller's T and policy
     c->state = ST_IDLE;
     return CGX_OK;
 }
@@ -480,8 +578,12 @@ int cgx_set_precond_block(cgx_ctx *c, int bs) {
     char *dD = nullptr;
     TRY(pc_alloc(s, (int64_t)cnt, &dD));
     auto extract = [&]() -> int {
-        HIPT(csr_diag_blocks_f64(c->n, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
-                                 reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(dD), s.stream));
+        if (c->bsr_bs)  // the same blocks from the BSR arrays, for any bs (cgx_bsmv.hip)
+            HIPT(bsr_diag_blocks_f64(c->n, c->bsr_bs, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                     reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(dD), s.stream));
+        else
+            HIPT(csr_diag_blocks_f64(c->n, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                     reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(dD), s.stream));
         HIPT(hipMemcpyAsync(D.data(), dD, cnt * 8, hipMemcpyDeviceToHost, s.stream));
         HIPT(hipStreamSynchronize(s.stream));
         return CGX_OK;
@@ -551,22 +653,12 @@ int cgx_get_precond_diag(cgx_ctx *c, double *minv) {
 }
 
 int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col_idx) {
-    if (n < 1 || nnz < 0) return fail(CGX_ERR_ARG, "cgx_csr_check: n must be >= 1 and nnz >= 0");
-    if (!row_ptr || (nnz > 0 && !col_idx)) return fail(CGX_ERR_ARG, "cgx_csr_check: NULL pointer");
-    if (row_ptr[0] != 0)
-        return fail(CGX_ERR_SHAPE, "cgx_csr_check: row_ptr[0] = %lld, must be 0", (long long)row_ptr[0]);
-    for (int64_t i = 0; i < n; ++i)
-        if (row_ptr[i + 1] < row_ptr[i])
-            return fail(CGX_ERR_SHAPE, "cgx_csr_check: row_ptr decreases at row %lld (%lld -> %lld)", (long long)i,
-                        (long long)row_ptr[i], (long long)row_ptr[i + 1]);
-    if (row_ptr[n] != nnz)
-        return fail(CGX_ERR_SHAPE, "cgx_csr_check: row_ptr[n] = %lld, must be nnz = %lld", (long long)row_ptr[n],
-                    (long long)nnz);
-    for (int64_t e = 0; e < nnz; ++e)
-        if (col_idx[e] < 0 || (int64_t)col_idx[e] >= n)
-            return fail(CGX_ERR_SHAPE, "cgx_csr_check: col_idx[%lld] = %d outside [0, %lld)", (long long)e,
-                        (int)col_idx[e], (long long)n);
-    return CGX_OK;
+    return structure_check({"cgx_csr_check", "n", "nnz", "row_ptr", "col_idx", "row"}, n, nnz, row_ptr, col_idx);
+}
+
+int cgx_bsr_check(int64_t nb, int64_t nnzb, const int64_t *brow_ptr, const int32_t *bcol_idx) {
+    return structure_check({"cgx_bsr_check", "nb", "nnzb", "brow_ptr", "bcol_idx", "block row"}, nb, nnzb, brow_ptr,
+                           bcol_idx);
 }
 
 int cgx_csr_halo_counts(int64_t n, int nshards, const int64_t *row_ptr, const int32_t *col_idx, int64_t *counts) {
@@ -635,6 +727,62 @@ int cgx_set_csr(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, cons
 int cgx_set_csr_f32(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx, const float *values) {
     const Range range_("cgx_set_csr_f32");
     return csr_upload(c, row_ptr, col_idx, values, /*f32=*/true, "cgx_set_csr_f32");
+}
+
+int cgx_set_bsr(cgx_ctx *c, int bs, const int64_t *brow_ptr, const int32_t *bcol_idx, const double *values) {
+    const Range range_("cgx_set_bsr");
+    if (!c) return fail(CGX_ERR_ARG, "cgx_set_bsr: ctx is NULL");
+    if (!brow_ptr) return fail(CGX_ERR_ARG, "cgx_set_bsr: brow_ptr is NULL");
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_bsr: not a cgx_create_csr context");
+    if (c->nr)
+        return fail(CGX_ERR_ARG, "cgx_set_bsr: not with several right-hand sides (a cgx_create_csr_nrhs context): "
+                                 "batched BSR is not built");
+    if (c->csr_multi)
+        return fail(CGX_ERR_ARG, "cgx_set_bsr: not over row blocks (a cgx_create_csr_multi context): BSR over row "
+                                 "blocks is not built");
+    if (bs == 1) return fail(CGX_ERR_ARG, "cgx_set_bsr: bs = 1 is scalar CSR: use cgx_set_csr");
+    if (bs < 2 || bs > CGX_MAX_BSR_BLOCK)
+        return fail(CGX_ERR_ARG, "cgx_set_bsr: bs must be in [2, %d] (got %d)", CGX_MAX_BSR_BLOCK, bs);
+    if (c->n % bs != 0)
+        return fail(CGX_ERR_SHAPE, "cgx_set_bsr: n = %lld is not divisible by bs = %d", (long long)c->n, bs);
+    const int64_t nb = c->n / bs, nnzb = brow_ptr[nb];  // the block count a valid brow_ptr states
+    if (nnzb < 0) return fail(CGX_ERR_SHAPE, "cgx_set_bsr: brow_ptr[nb] = %lld is negative", (long long)nnzb);
+    if (nnzb > 0 && (!bcol_idx || !values)) return fail(CGX_ERR_ARG, "cgx_set_bsr: bcol_idx / values is NULL");
+    if (nnzb > c->csr_cap / (bs * bs))  // nnzb bs^2 > the room, without the product's overflow
+        return fail(CGX_ERR_SHAPE, "cgx_set_bsr: %lld blocks of %d x %d are %.0f entries, the context has room for %lld",
+                    (long long)nnzb, bs, bs, (double)nnzb * (bs * bs), (long long)c->csr_cap);
+    TRY(cgx_bsr_check(nb, nnzb, brow_ptr, bcol_idx));  // nothing is uploaded when it fails
+    return bsr_upload(c, bs, nnzb, brow_ptr, bcol_idx, values);
+}
+
+int cgx_bsr_tile_values(int64_t nnzb, int bs, const void *values, void *values_tiled, void *stream) {
+    if (bs < 2 || bs > CGX_MAX_BSR_BLOCK)
+        return fail(CGX_ERR_ARG, "cgx_bsr_tile_values: bs must be in [2, %d] (got %d)", CGX_MAX_BSR_BLOCK, bs);
+    if (nnzb < 0) return fail(CGX_ERR_SHAPE, "cgx_bsr_tile_values: bad block count");
+    if (!values || !values_tiled) return fail(CGX_ERR_ARG, "cgx_bsr_tile_values: NULL pointer");
+    HIPT(bsr_tile_values_f64(nnzb, bs, static_cast<const double *>(values), static_cast<double *>(values_tiled),
+                             static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
+int cgx_spmv_bsr(int64_t nb, int64_t ncolb, int bs, const void *brow_ptr, const void *bcol_idx,
+                 const void *values_tiled, const void *v, void *out, void *stream) {
+    if (bs < 2 || bs > CGX_MAX_BSR_BLOCK)
+        return fail(CGX_ERR_ARG, "cgx_spmv_bsr: bs must be in [2, %d] (got %d)", CGX_MAX_BSR_BLOCK, bs);
+    if (nb < 0 || ncolb < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_bsr: bad shape");
+    if (!brow_ptr || !bcol_idx || !values_tiled || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_bsr: NULL pointer");
+    if (bs % 2 == 0 && (reinterpret_cast<uintptr_t>(v) & 15))
+        return fail(CGX_ERR_ARG, "cgx_spmv_bsr: v must be 16-byte aligned when bs is even (the kernel's loads of v)");
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    RedWs ws;
+    TRY(dev_ws(&ws));
+    // the block count lives on the device: T comes from CGX_BSMV_PLAN or, without it, is 8
+    const MatvecPlan pl = plan_spmv_bsr(dev, nb, /*nnzb=*/-1, bs);
+    HIPT(spmv_bsr_f64(pl, bs, static_cast<const int64_t *>(brow_ptr), static_cast<const int32_t *>(bcol_idx),
+                      static_cast<const double *>(values_tiled), nb, static_cast<const double *>(v),
+                      static_cast<double *>(out), nullptr, nullptr, ws, static_cast<hipStream_t>(stream)));
+    return CGX_OK;
 }
 
 int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx, const void *values,

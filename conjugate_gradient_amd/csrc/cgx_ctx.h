@@ -4,7 +4,7 @@
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
 //   cgx_nrhs.hip      cgx_create_nrhs / cgx_create_csr_nrhs contexts: several systems per pass over A
-//   cgx_csr.hip       cgx_create_csr / cgx_create_csr_multi contexts: A in CSR storage (structure check, upload, the row blocks' exchange lists), diagonal and block preconditioning
+//   cgx_csr.hip       cgx_create_csr / cgx_create_csr_multi contexts: A in CSR or block (BSR) storage (structure check, upload, the row blocks' exchange lists), diagonal and block preconditioning
 //   cgx_pcblock.hip   block Jacobi's host side: the blocks' Cholesky inversion and the check of a caller's blocks
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
@@ -190,6 +190,12 @@ struct Shard {
     // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap], or the
     // first half of it as float[csr_cap] while cgx_ctx::csr_f32); no s.A
     char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
+    // cgx_set_bsr (cgx_ctx::bsr_bs > 0): csr_rp holds brow_ptr (int64[nb + 1]), csr_ci bcol_idx (int32[nnzb]),
+    // csr_val the values in the host layout (what the preconditioners' extraction reads), and bsr_val the same
+    // values in k_bsr_mult_f64's tiled layout: bsr_cap doubles, the library's own memory beside the context's
+    // capacity, allocated by the first cgx_set_bsr that needs it and kept until the context goes
+    char *bsr_val = nullptr;
+    int64_t bsr_cap = 0;
     // cgx_create_csr_multi: this block's rows only (row_ptr rebased to 0, col_idx still global), and its exchange
     // lists -- for every other block q the ascending offsets into q's slice that this block's col_idx names, source
     // after source in halo_idx (int32[halo_cap]), list q at halo.off[q] .. halo.off[q + 1]
@@ -303,6 +309,10 @@ struct cgx_ctx {
     int64_t csr_cap = 0, csr_nnz = -1;
     bool csr_plan_user = false;
     bool csr_f32 = false;
+    // cgx_set_bsr: the block size while the context is block-valued (0: scalar CSR; the next cgx_set_csr /
+    // cgx_set_csr_f32 goes back to 0), and its stored blocks; csr_nnz is then bsr_nnzb * bsr_bs^2
+    int bsr_bs = 0;
+    int64_t bsr_nnzb = 0;
     // cgx_create_csr_multi (whatever the block count): csr_cap is every block's room; halo_counts[d * S + q] =
     // the length of block d's list into block q (cgx_get_csr_halo); csr_halo: several blocks exchange p and x
     // through those lists (gather_indexed; false: whole slices, CGX_CSR_XCHG=full or CGX_LOCAL_XCHG=copy)

@@ -86,6 +86,7 @@ struct MatvecPlan {
     int a32 = 0;      // 1: k_matvec_a32's plan (float A; U counts 256-column chunks, nt is 2 or 8)
     int nrhs = 0;     // > 0: k_matvec_nrhs_f64's plan for this many vectors per pass (2, 4 or 8; nt is 2 or 8)
     int csr = 0;      // 1: k_csr_mult_f64's plan (R = 64 / T rows per wave, U = 1, nt is 2 or 8)
+    int bsr = 0;      // > 0 (with csr = 1): k_bsr_mult_f64's plan for this block size (R = 64 / T block rows per wave)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -231,6 +232,37 @@ MatvecPlan plan_spmv_csr(int device, int64_t rows, int64_t nnz, int T = 0, int n
 hipError_t spmv_csr_f64(const MatvecPlan &pl, const int64_t *row_ptr, const int32_t *col_idx, CsrValues values,
                         int64_t rows, const double *v, double *out, const double *pown, double *dot_out,
                         const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
+
+// ---- sparse A in block (BSR) storage (cgx_bsmv.hip) --------------------------------
+// out[I bs + i] = sum over the blocks q in [brow_ptr[I], brow_ptr[I+1]) and j < bs of
+// B_q[i][j] * v[bcol_idx[q] bs + j], blocks in stored order, j ascending, T = 64 / pl.R
+// lanes per block row (the order contract and the device layout of the values are in
+// cgx_bsmv.hip); pown != nullptr: also *dot_out = pown . out (fixed order for a fixed
+// grid).  `tiled` holds bsr_tiled_count(nnzb, bs) doubles in the tiled layout
+// (bsr_tile_values_f64 re-lays the host layout: block after block, row-major inside
+// one).  The indices are not range-checked here (cgx_bsr_check); v is 16-byte aligned
+// when bs is even (hipErrorInvalidValue otherwise).
+// The instantiated (bs, T, policy): bs in 2..8, T in {2, 4, 8, 16, 32, 64}, policy 2 or 8.
+constexpr int kMaxBsrBlock = 8;
+inline int64_t bsr_tiled_count(int64_t nnzb, int bs) { return (nnzb + 63) / 64 * 64 * bs * bs; }
+bool spmv_bsr_plan_ok(int bs, int T, int nt);
+// T <= 0 / nt < 0 / blocks_per_cu <= 0 pick the defaults (T from the mean blocks per
+// block row nnzb / nb, 8 when nnzb < 0; env CGX_BSMV_PLAN="T=..,nt=..,bpc=.." may
+// override with an instantiated plan).  pl.csr = 1, pl.bsr = bs.
+MatvecPlan plan_spmv_bsr(int device, int64_t nb, int64_t nnzb, int bs, int T = 0, int nt = -1, int blocks_per_cu = 0);
+hipError_t spmv_bsr_f64(const MatvecPlan &pl, int bs, const int64_t *brow_ptr, const int32_t *bcol_idx,
+                        const double *tiled, int64_t nb, const double *v, double *out, const double *pown,
+                        double *dot_out, const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr,
+                        int64_t *ts = nullptr);
+hipError_t bsr_tile_values_f64(int64_t nnzb, int bs, const double *values, double *tiled, hipStream_t s);
+// The preconditioners' one-time extraction from the BSR arrays (values in the host
+// layout), bit for bit what csr_diag_minv_f64 / csr_diag_blocks_f64 (below) give on
+// the expanded matrix -- row I bs + i's entries block after block in stored order, j
+// ascending inside a block; pbs: the preconditioner's block size, any of 2..kMaxPcBlock.
+hipError_t bsr_diag_minv_f64(int64_t n, int bs, const int64_t *brow_ptr, const int32_t *bcol_idx, const double *values,
+                             double *minv, unsigned long long *bad, hipStream_t s);
+hipError_t bsr_diag_blocks_f64(int64_t n, int bs, int pbs, const int64_t *brow_ptr, const int32_t *bcol_idx,
+                               const double *values, double *D, hipStream_t s);
 
 // ---- several right-hand sides on a CSR matrix (cgx_spmm.hip) ----------------------
 // Out[j*ldo + i] = sum over row i's entries of values[e] * V[j*ldv + col_idx[e]]
@@ -486,16 +518,17 @@ hipError_t preload_spmv();
 hipError_t preload_spmm();
 hipError_t preload_pcg();
 hipError_t preload_pcg_block();
+hipError_t preload_bsmv();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
-    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512, PL_PCG_BLOCK = 1024
+    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512, PL_PCG_BLOCK = 1024, PL_BSMV = 2048
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
         {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg},
-        {PL_SPMM, preload_spmm}, {PL_PCG_BLOCK, preload_pcg_block}};
+        {PL_SPMM, preload_spmm}, {PL_PCG_BLOCK, preload_pcg_block}, {PL_BSMV, preload_bsmv}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

@@ -325,6 +325,70 @@
  *       non-NULL A.  cgx_solve_begin, cgx_solve, cgx_residual_norm and
  *       cgx_get_csr_halo before the first cgx_set_csr: CGX_ERR_STATE.
  *       cgx_create_csr_nrhs stays one GPU.
+ *   - Block storage (cgx_set_bsr, on a plain cgx_create_csr context): systems
+ *     with bs coupled unknowns per node -- the ones cgx_set_precond_block was
+ *     built for -- are block matrices, every nonzero a dense bs x bs block.
+ *     Held as BSR an entry streams 8 + 4 / bs^2 bytes in place of CSR's 12 and
+ *     a block reads its bs vector elements as one contiguous piece in place of
+ *     bs^2 gathers.  2 <= bs <= CGX_MAX_BSR_BLOCK; bs = 1 is cgx_set_csr.
+ *     - Storage (scipy's bsr_matrix): brow_ptr is int64_t[nb + 1], bcol_idx
+ *       int32_t[nnzb], values double[nnzb * bs * bs], block after block,
+ *       row-major inside a block; n = nb * bs.  Block row I owns the blocks
+ *       [brow_ptr[I], brow_ptr[I+1]) in stored order: block columns need not
+ *       be sorted, a duplicate block column is two terms, a stored zero is a
+ *       term.
+ *     - Summation order (k_bsr_mult_f64, T lanes per block row, T = 2 .. 64).
+ *       For scalar row I bs + i, with s = brow_ptr[I]: sub-lane l starts from
+ *       +0.0 and, for each of its blocks s+l, s+l+T, ... in that order and
+ *       j = 0 .. bs-1 ascending inside a block in block column c, does
+ *       acc_i = fma(B[i][j], v[c bs + j], acc_i); the T partial sums are
+ *       combined as v[l] += v[l ^ o] for o = T/2, ..., 1.  A row's sum depends
+ *       on (bs, T) only -- not on the load policy, the grid, the trips in
+ *       flight, the row's place in a wave or the device layout of the values;
+ *       an empty block row gives bs values of +0.0.  The fused p.Ap: the
+ *       storing lane adds its bs rows in ascending order, then as the CSR
+ *       kernel's; deterministic for a given (bs, T, grid).
+ *     - On the device the values lie in tiles of 64 consecutive blocks,
+ *       entry-major inside a tile (entry e of block q at
+ *       ((q / 64) bs^2 + e) 64 + q % 64), so a wave's loads are contiguous.
+ *       cgx_set_bsr re-lays them once with a kernel into memory of the
+ *       library's own (ceil(nnzb / 64) 64 bs^2 doubles, beside the host-layout
+ *       copy the preconditioner set-up reads); it is not charged to the
+ *       context's capacity.
+ *     - cgx_set_bsr checks, in this order: a NULL context or brow_ptr
+ *       (CGX_ERR_ARG); not a plain cgx_create_csr context -- cgx_create_csr_nrhs
+ *       and cgx_create_csr_multi included, batched and row-block BSR are not
+ *       built (CGX_ERR_ARG); bs outside [2, 8] (CGX_ERR_ARG); n % bs != 0
+ *       (CGX_ERR_SHAPE); a NULL bcol_idx or values with nnzb > 0
+ *       (CGX_ERR_ARG); nnzb bs^2 above the creation-time nnz (CGX_ERR_SHAPE,
+ *       both counts named); cgx_bsr_check, cgx_csr_check's rules on the block
+ *       structure with nb block columns, the first offence named.  Nothing is
+ *       uploaded when one fails: the earlier matrix (CSR or BSR), its value
+ *       type, its plan and its preconditioner stay, and a later solve gives
+ *       the bits it gave before.
+ *     - A successful call ends a solve in progress, turns preconditioning
+ *       off, makes a new default plan unless the caller chose one (then T and
+ *       the policy are kept), and makes the context block-valued until the
+ *       next cgx_set_csr / cgx_set_csr_f32, after which the context gives a
+ *       fresh CSR context's bits again.  cgx_get_info: flags carries
+ *       CGX_BSR_ACTIVE | CGX_CSR_ACTIVE while the context is block-valued.
+ *     - cgx_set_matvec_plan: rows_per_wave = 64 / T counts block rows,
+ *       chunks_in_flight = 1, load policy 2 or 8, refusals as on CSR.  The
+ *       default T is the largest instantiated T <= the mean blocks per block
+ *       row, at least 2, policy 2 (measured at bs = 3 and 4);
+ *       CGX_BSMV_PLAN="T=..,nt=..,bpc=.." overrides it.
+ *     - The iteration is untouched: the three-launch one in every host form,
+ *       x the same bits across them for a given plan; only the matVec (and
+ *       cgx_residual_norm's) is the block kernel.
+ *     - Preconditioners: cgx_set_precond_diag and
+ *       cgx_set_precond_block_values never read the matrix.  CGX_PC_JACOBI and
+ *       cgx_set_precond_block(pbs), any pbs in 2..8 and not only pbs == bs,
+ *       extract from the BSR arrays and give, bit for bit, the 1 / diag(A) and
+ *       the diagonal blocks a double-valued CSR context gives on the expanded
+ *       matrix (scalar row I bs + i's entries listed block after block in
+ *       stored order, j ascending inside a block); the failures are CSR's.
+ *     - Not built: float-stored BSR values, several right-hand sides, several
+ *       row blocks, bs = 1, a rectangular block shape.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -357,7 +421,8 @@ extern "C" {
                            only; CGX_A_F32 is also reported by a float-valued CSR context); likewise
                            cgx_create_csr_multi, cgx_csr_halo_counts, cgx_csr_halo_list,
                            cgx_get_csr_halo and cgx_gather_indexed, and the reported bit
-                           CGX_CSR_HALO_ACTIVE */
+                           CGX_CSR_HALO_ACTIVE; likewise cgx_set_bsr, cgx_bsr_check, cgx_spmv_bsr and
+                           cgx_bsr_tile_values, and the reported bit CGX_BSR_ACTIVE */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -480,6 +545,8 @@ extern "C" {
 #define CGX_CSR_HALO_ACTIVE 0x20000000 /* reported in cgx_info.flags: a cgx_create_csr_multi context whose
                                          row blocks exchange p by index lists (k_gather_indexed; else whole
                                          slices: CGX_CSR_XCHG=full, CGX_LOCAL_XCHG=copy, or one block) */
+#define CGX_BSR_ACTIVE 0x40000000 /* reported in cgx_info.flags: a cgx_create_csr context that is block-valued
+                                     (cgx_set_bsr), beside CGX_CSR_ACTIVE */
 
 typedef struct cgx_ctx cgx_ctx;
 
@@ -691,6 +758,16 @@ int cgx_set_csr(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, co
  * above): the context gives the bits a double-valued one gives on (double)values[e].  The same
  * checks, refusals and effects as cgx_set_csr; a failed call also leaves the value type as it was. */
 int cgx_set_csr_f32(cgx_ctx *ctx, const int64_t *row_ptr, const int32_t *col_idx, const float *values);
+/* ---- block (BSR) storage on a cgx_create_csr context (see "Block storage" above) ---------- */
+#define CGX_MAX_BSR_BLOCK 8
+/* Host-only: cgx_csr_check's rules on a block structure of nb block rows and nb block columns:
+ * brow_ptr[0] != 0, brow_ptr decreasing at block row I, brow_ptr[nb] != nnzb, bcol_idx[q] outside
+ * [0, nb) -- CGX_ERR_SHAPE with the first offence named. */
+int cgx_bsr_check(int64_t nb, int64_t nnzb, const int64_t *brow_ptr, const int32_t *bcol_idx);
+/* Host arrays in scipy's bsr_matrix layout (brow_ptr[n / bs] blocks of bs x bs, nnzb * bs * bs at most
+ * the context's nnz), 2 <= bs <= CGX_MAX_BSR_BLOCK; makes a plain cgx_create_csr context block-valued
+ * until the next cgx_set_csr / cgx_set_csr_f32.  Checks and effects: "Block storage" above. */
+int cgx_set_bsr(cgx_ctx *ctx, int bs, const int64_t *brow_ptr, const int32_t *bcol_idx, const double *values);
 /* One GPU, fp64: nrhs (1..CGX_MAX_NRHS) systems A x_j = b_j on one CSR matrix with room for
  * nnz entries, solved together, one read of the CSR arrays per iteration.
  * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
@@ -866,6 +943,17 @@ int cgx_spmv_csr(int64_t rows, int64_t cols, const void *row_ptr, const void *co
  * (double)values[e] at the same T.  Plan from CGX_SPMV_PLAN as above. */
 int cgx_spmv_csr_f32(int64_t rows, int64_t cols, const void *row_ptr, const void *col_idx,
                      const float *values, const void *v, void *out, void *stream);
+/* Kernel-level, device pointers: values_tiled (ceil(nnzb / 64) * 64 * bs * bs doubles) = values
+ * (nnzb * bs * bs doubles, block after block, row-major inside a block) in k_bsr_mult_f64's tiled
+ * layout, the pad of the last tile +0.0.  2 <= bs <= CGX_MAX_BSR_BLOCK. */
+int cgx_bsr_tile_values(int64_t nnzb, int bs, const void *values, void *values_tiled, void *stream);
+/* Kernel-level, device pointers: out[I*bs + i] = sum over the blocks q in [brow_ptr[I], brow_ptr[I+1])
+ * and j < bs of B_q[i][j] * v[bcol_idx[q]*bs + j], I < nb, in the order of "Block storage" above; v has
+ * ncolb * bs entries and is 16-byte aligned when bs is even (CGX_ERR_ARG otherwise), values_tiled comes
+ * from cgx_bsr_tile_values.  The indices must have passed cgx_bsr_check: the kernel does not
+ * range-check them.  T comes from CGX_BSMV_PLAN="T=..,nt=..,bpc=.." (default T = 8). */
+int cgx_spmv_bsr(int64_t nb, int64_t ncolb, int bs, const void *brow_ptr, const void *bcol_idx,
+                 const void *values_tiled, const void *v, void *out, void *stream);
 /* Kernel-level, device pointers: Out[j*ldo + i] = sum_e values[e] * V[j*ldv + col_idx[e]],
  * j < nrhs.  Column j is cgx_spmv_csr's result on column j bit for bit at the same T.
  * The indices must have passed cgx_csr_check.  T comes from
