@@ -40,6 +40,7 @@ __all__ = [
     "CGX_MAX_NRHS", "matVec_nrhs",
     "CGX_CSR_ACTIVE", "spmv_csr", "spmm_csr",
     "CGX_BSR_ACTIVE", "CGX_MAX_BSR_BLOCK", "bsr_check", "spmv_bsr",
+    "CGX_DIA_ACTIVE", "dia_check", "spmv_dia",
     "CGX_CSR_HALO_ACTIVE", "csr_halo_counts", "csr_halo_list", "gather_indexed",
     "CGX_PRECOND_ACTIVE", "PRECOND_KINDS", "PC_BLOCK", "CGX_MAX_PC_BLOCK", "csr_diag_blocks", "precond_block_invert",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
@@ -74,6 +75,7 @@ CGX_PRECOND_ACTIVE = 0x10000000  # reported in info.flags: a CSR context iterati
 CGX_CSR_HALO_ACTIVE = 0x20000000
 CGX_BSR_ACTIVE = 0x40000000  # reported in info.flags beside CGX_CSR_ACTIVE: a CSR solver that is block-valued (set_bsr)
 CGX_MAX_BSR_BLOCK = 8  # the largest block size of set_bsr
+CGX_DIA_ACTIVE = 0x4  # reported in info.flags beside CGX_CSR_ACTIVE: a CSR solver that is diagonal-valued (set_dia)
 # cgx_set_precond's kinds, CGX_PC_NONE / CGX_PC_JACOBI / CGX_PC_DIAG (include/cgx.h), by the names Solver.precond
 # reports.  Kept out of the CGX_* names: those are the flag words, and a kind is not a bit of one.
 PRECOND_KINDS = {"none": 0, "jacobi": 1, "diag": 2}
@@ -197,6 +199,9 @@ def lib() -> ctypes.CDLL:
         "cgx_set_bsr": ([vp, i32, vp, vp, vp], i32),
         "cgx_bsr_tile_values": ([i64, i32, vp, vp, vp], i32),
         "cgx_spmv_bsr": ([i64, i64, i32, vp, vp, vp, vp, vp, vp], i32),
+        "cgx_dia_check": ([i64, i64, vp], i32),
+        "cgx_set_dia": ([vp, i64, vp, vp, i64], i32),
+        "cgx_spmv_dia": ([i64, i64, vp, vp, i64, vp, vp, vp], i32),
         "cgx_spmv_csr_f32": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_create_csr_nrhs": ([pctx, i64, i64, i32, i32, i32], i32),
         "cgx_create_csr_multi": ([pctx, i64, i64, i32, ctypes.POINTER(i32), i32], i32),
@@ -554,6 +559,59 @@ def _bsr_arrays(what: str, indptr, indices=None, data=None):
     _need(2 <= bs <= CGX_MAX_BSR_BLOCK, f"{what}: bs must be in [2, {CGX_MAX_BSR_BLOCK}] (got {bs})")
     _need(ci.size == va.shape[0], f"{what}: {ci.size} indices but {va.shape[0]} blocks")
     return rp, ci, va, bs
+
+
+def _dia_arrays(what: str, offsets, data=None):
+    """(offsets int32[ndiag], data float64 of shape (ndiag, ld)), contiguous, scipy's dia_matrix layout
+    (``data[k, j] = A[j - offsets[k], j]``); ``offsets`` may be an object with ``.offsets / .data`` such as scipy's
+    dia_matrix (no scipy needed)."""
+    if data is None and hasattr(offsets, "offsets"):
+        offsets, data = offsets.offsets, offsets.data
+    _need(data is not None, f"{what}: offsets and data are needed")
+    d = np.asarray(data)
+    o = np.asarray(offsets)
+    _need(d.dtype.kind in "fiu", f"{what}: data must be real numbers (got {d.dtype})")
+    _need(o.dtype.kind in "iu" or o.size == 0, f"{what}: offsets must be integers (got {o.dtype})")
+    _need(o.ndim == 1, f"{what}: offsets are one-dimensional")
+    _need(d.ndim == 2, f"{what}: data must have shape (ndiag, ld) (got {d.shape})")
+    _need(o.size == d.shape[0], f"{what}: {o.size} offsets but {d.shape[0]} diagonals")
+    _need(o.size == 0 or (int(o.min()) >= -2**31 and int(o.max()) < 2**31), f"{what}: an offset does not fit int32")
+    return np.ascontiguousarray(o, np.int32), np.ascontiguousarray(d, np.float64)
+
+
+def dia_check(offsets, n: int) -> None:
+    """cgx_dia_check (host only, no GPU): raises CgxError(-4) naming the first offset outside (-n, n)."""
+    o = np.asarray(offsets)
+    _need(o.ndim == 1 and (o.dtype.kind in "iu" or o.size == 0), "dia_check: offsets are one-dimensional integers")
+    _need(isinstance(n, (int, np.integer)), "dia_check: n is an integer")
+    _need(o.size == 0 or (int(o.min()) >= -2**31 and int(o.max()) < 2**31), "dia_check: an offset does not fit int32")
+    o = np.ascontiguousarray(o, np.int32)
+    _check(lib().cgx_dia_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_check")
+
+
+def spmv_dia(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> None:
+    """out[i] = sum over the diagonals k, in stored order, with 0 <= i + offsets[k] < n of
+    data[k, i + offsets[k]] * v[i + offsets[k]], i < n (k_dia_mult_f64; the plan from CGX_DIA_PLAN).  ``data`` has
+    shape (ndiag, ld), ld >= n, scipy's dia_matrix layout.  The offsets come as a host array: they are checked
+    (cgx_dia_check) and only then uploaded; slots of ``data`` that hold no entry of A are never read by the kernel."""
+    o, d = _dia_arrays("spmv_dia", offsets, data)
+    _need(isinstance(n, (int, np.integer)) and n >= 1, "spmv_dia: need an integer n >= 1")
+    ld = int(d.shape[1])
+    _need(ld >= n, f"spmv_dia: data has {ld} columns, n = {n} needed")
+    _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_dia: float64 only")
+    _fits([v], n, "spmv_dia v")
+    _fits([out], n, "spmv_dia out")
+    L = lib()
+    _check(L.cgx_dia_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_check")
+    ndiag = int(o.size)
+    d_o = DeviceArray.from_host(o if ndiag else np.zeros(1, np.int32))
+    d_d = DeviceArray.from_host(d.reshape(-1) if ndiag else np.zeros(1))
+    try:
+        _check(L.cgx_spmv_dia(int(n), ndiag, d_o.ptr, d_d.ptr, ld, v.ptr, out.ptr, None), "cgx_spmv_dia")
+        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
+    finally:
+        for a in (d_o, d_d):
+            a.free()
 
 
 def bsr_check(indptr, indices, nb: int | None = None) -> None:
@@ -943,6 +1001,48 @@ class Solver:
               f"set_bsr: {ci.size} blocks of {bs} x {bs} are {ci.size * bs * bs} entries, the solver has room for "
               f"{self.csr_nnz}")
         _check(lib().cgx_set_bsr(self._h, bs, _ptr(rp), _ptr(ci), _ptr(va)), "cgx_set_bsr")
+
+    @classmethod
+    def from_dia(cls, offsets, data=None, *, n: int | None = None, precond=None, device: int = 0,
+                 flags: int = CGX_F64) -> "Solver":
+        """A CSR solver sized for this matrix held by diagonals (room for ndiag * n entries), with the matrix set
+        through :meth:`set_dia` (b = 0, x0 = 0) and, with ``precond`` ("jacobi", an array or ``("block", pbs)``),
+        its preconditioner (:meth:`set_precond`).  ``data`` has shape (ndiag, ld); or pass one object with
+        ``.offsets / .data`` such as scipy's dia_matrix.  ``n`` defaults to the object's ``shape[0]``, else to ld."""
+        if n is None and data is None and hasattr(offsets, "shape") and hasattr(offsets, "offsets"):
+            n = int(offsets.shape[0])
+        o, d = _dia_arrays("from_dia", offsets, data)
+        n = int(d.shape[1]) if n is None else n
+        _need(isinstance(n, (int, np.integer)) and n >= 1, f"from_dia: n must be an integer >= 1 (got {n})")
+        _need(d.shape[1] >= n, f"from_dia: data has {d.shape[1]} columns, n = {n} needed")
+        s = cls.csr(int(n), int(o.size) * int(n), device=device, flags=flags)
+        try:
+            s.set_dia(o, d)
+            if precond is not None:
+                s.set_precond(precond)
+        except Exception:
+            s.close()
+            raise
+        return s
+
+    def set_dia(self, offsets, data=None) -> None:
+        """cgx_set_dia: the matrix of a ``csr_nnz`` solver held by diagonals, scipy's dia_matrix layout (``data`` of
+        shape (ndiag, ld), ld >= n, ``data[k, j] = A[j - offsets[k], j]``; or one object with ``.offsets / .data``),
+        multiplied by the gather-free kernel k_dia_mult_f64.  Slots that hold no entry of A are never read and may
+        hold NaN.  The offsets are checked before anything is uploaded: CgxError(-4) names the first offence and the
+        earlier matrix stays.  The solver is diagonal-valued (``info().flags`` carries CGX_DIA_ACTIVE) until the
+        next :meth:`set_csr` / :meth:`set_bsr`; preconditioning is off afterwards, as after ``set_csr``.  One GPU,
+        one right-hand side, float64 values."""
+        _need(getattr(self, "csr_nnz", None) is not None, "set_dia: the solver was not created with csr_nnz=")
+        _need(getattr(self, "devices", None) is None and getattr(self, "nrhs", None) is None,
+              "set_dia: diagonal storage runs on one GPU with one right-hand side (not with devices= or nrhs=)")
+        o, d = _dia_arrays("set_dia", offsets, data)
+        _need(d.shape[1] >= self.n, f"set_dia: data has {d.shape[1]} columns, n = {self.n} needed")
+        _need(o.size * self.n <= self.csr_nnz,
+              f"set_dia: {o.size} diagonals of {self.n} rows are {o.size * self.n} entries, the solver has room for "
+              f"{self.csr_nnz}")
+        _check(lib().cgx_set_dia(self._h, int(o.size), _ptr(o) if o.size else None, _ptr(d) if o.size else None,
+                                 int(d.shape[1])), "cgx_set_dia")
 
     def csr_halo(self) -> np.ndarray:
         """cgx_get_csr_halo: the ``(nshards, nshards)`` exchange counts in use on a CSR solver over row blocks

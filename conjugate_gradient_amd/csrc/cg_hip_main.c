@@ -52,7 +52,12 @@
  * --bsr BS (with --csr, 2 <= BS <= 8 dividing N: every BS x BS block of the
  * matrix that holds an entry is kept whole, zero-filled, and the solve runs
  * through cgx_set_bsr and the block kernel; takes --jacobi or --block-jacobi
- * as --csr does, not --csr-a32; --stats adds "nnzb: <count>").
+ * as --csr does, not --csr-a32; --stats adds "nnzb: <count>"),
+ * --dia (with --csr: every diagonal of the matrix that holds an entry is kept
+ * whole, offsets ascending, zero-filled, and the solve runs through
+ * cgx_set_dia and the gather-free diagonal kernel; takes --jacobi or
+ * --block-jacobi as --csr does, not --csr-a32 or --bsr; --stats adds
+ * "ndiag: <count>").
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -140,8 +145,10 @@ static void usage(const char *prog) {
             "       %s --csr-a32 [--jacobi | --block-jacobi BS] ... (--csr with the values parsed and kept as float, fp64\n"
             "          arithmetic; given without --csr)\n"
             "       %s --csr --bsr BS [--jacobi | --block-jacobi BS] ... (--csr held as dense BS x BS blocks, BS in 2..8\n"
-            "          dividing N, multiplied by the block kernel; not with --csr-a32)\n",
-            prog, prog, prog, prog, prog, prog);
+            "          dividing N, multiplied by the block kernel; not with --csr-a32)\n"
+            "       %s --csr --dia [--jacobi | --block-jacobi BS] ... (--csr held as the diagonals that hold an entry,\n"
+            "          multiplied by the diagonal kernel; not with --csr-a32 or --bsr)\n",
+            prog, prog, prog, prog, prog, prog, prog);
 }
 
 static int die_cgx(int rc, const char *what) {
@@ -390,6 +397,38 @@ static int bsr_from_csr(const csr_host *m, int64_t n, int bs, bsr_host *out) {
     return 0;
 }
 
+/* --dia: the CSR arrays of csr_parse by diagonals -- every diagonal that holds
+ * an entry, offsets ascending, the rest of a diagonal +0.0; data[k * n + j] =
+ * A[j - offsets[k]][j] (values double).  Returns 0, or -9 when memory runs out. */
+typedef struct {
+    int32_t *offsets;
+    double *data;
+    int64_t ndiag;
+} dia_host;
+
+static int dia_from_csr(const csr_host *m, int64_t n, dia_host *out) {
+    const double *val = (const double *)m->values;
+    int64_t *slot = malloc((size_t)(2 * n - 1) * sizeof(int64_t)); /* offset o's diagonal at slot[o + n - 1], or -1 */
+    if (!slot) return -9;
+    for (int64_t d = 0; d < 2 * n - 1; ++d) slot[d] = -1;
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = m->row_ptr[i]; e < m->row_ptr[i + 1]; ++e) slot[m->col_idx[e] - i + n - 1] = 0;
+    int64_t ndiag = 0;
+    for (int64_t d = 0; d < 2 * n - 1; ++d)
+        if (slot[d] == 0) slot[d] = ndiag++;
+    out->ndiag = ndiag;
+    out->offsets = malloc((size_t)(ndiag > 0 ? ndiag : 1) * sizeof(int32_t));
+    out->data = calloc((size_t)(ndiag > 0 ? ndiag : 1) * (size_t)n, sizeof(double));
+    if (!out->offsets || !out->data) { free(slot); return -9; }
+    for (int64_t d = 0; d < 2 * n - 1; ++d)
+        if (slot[d] >= 0) out->offsets[slot[d]] = (int32_t)(d - (n - 1));
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = m->row_ptr[i]; e < m->row_ptr[i + 1]; ++e)
+            out->data[slot[m->col_idx[e] - i + n - 1] * n + m->col_idx[e]] = val[e];
+    free(slot);
+    return 0;
+}
+
 /* Whole-string numeric option values: "--eps abc" or "--gpus 2x" is an
  * error (exit 2), not a silent 0. */
 static int opt_ll(const char *name, const char *v, long long *out) {
@@ -418,6 +457,7 @@ int main(int argc, char **argv) {
     double eps = EPSILON_DEFAULT;
     long long max_iter = -1, n_opt = -1, spd_n = -1, nrhs = 0, block_bs = 0; /* block_bs > 0: --block-jacobi */
     long long bsr_bs = 0; /* > 0: --bsr */
+    int dia = 0;          /* --dia */
     unsigned long long seed = 42;
     const char *dims_path = NULL;
     const char *pos[3];
@@ -449,7 +489,8 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "--bsr must be an integer in [2, %d]\n", CGX_MAX_BSR_BLOCK);
                 return 2;
             }
-        } else if (!strcmp(a, "--eps") && has_val) {
+        } else if (!strcmp(a, "--dia")) dia = 1;
+        else if (!strcmp(a, "--eps") && has_val) {
             if (!opt_double(a, argv[++i], &eps)) return 2;
         } else if (!strcmp(a, "--max-iter") && has_val) {
             if (!opt_ll(a, argv[++i], &max_iter)) return 2;
@@ -487,6 +528,10 @@ int main(int argc, char **argv) {
     }
     if (bsr_bs > 0 && (csr_a32 || !csr)) {
         fprintf(stderr, "--bsr holds a --csr matrix as dense blocks of double values: it is given with --csr (not --csr-a32)\n");
+        return 2;
+    }
+    if (dia && (csr_a32 || bsr_bs > 0 || !csr)) {
+        fprintf(stderr, "--dia holds a --csr matrix by its diagonals, double values: it is given with --csr (not --csr-a32 or --bsr)\n");
         return 2;
     }
     if (csr_a32) csr = 1;
@@ -597,6 +642,7 @@ int main(int argc, char **argv) {
     create_job job = {n, gpus, flags, CGX_OK, (int)nrhs, NULL, 0.0, 0.0, csr, -1};
     csr_host csrm = {NULL, NULL, NULL, 0, 0};
     bsr_host bsrm = {NULL, NULL, NULL, 0};
+    dia_host diam = {NULL, NULL, 0};
     const double t_start = now_s();
     pthread_t creator;
     const int threaded = pthread_create(&creator, NULL, create_ctx, &job) == 0;
@@ -640,6 +686,10 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "can't allocate memory for vector\n");
                 read_rc = -9;
             }
+            if (!read_rc && dia && dia_from_csr(&csrm, n, &diam) != 0) {
+                fprintf(stderr, "can't allocate memory for vector\n");
+                read_rc = -9;
+            }
         }
         t_parsed = now_s();
         if (threaded) pthread_join(creator, NULL); /* before any exit: HIP may be starting up on it */
@@ -648,6 +698,7 @@ int main(int argc, char **argv) {
         rel.text = text;
         if (!read_rc) {
             job.csr_nnz = bsr_bs > 0 ? bsrm.nnzb * bsr_bs * bsr_bs : csrm.nnz; /* blocks are stored whole */
+            if (dia && diam.ndiag * n > job.csr_nnz) job.csr_nnz = diam.ndiag * n; /* and so are diagonals */
             create_ctx(&job);
         }
     } else if (stream_a) {
@@ -746,10 +797,11 @@ int main(int argc, char **argv) {
         t_dist1 = now_s();
         if (rc != CGX_OK) return die_cgx(rc, "cgx_generate_spd");
     } else if (csr) {
-        rc = bsr_bs > 0 ? cgx_set_bsr(ctx, (int)bsr_bs, bsrm.brow_ptr, bsrm.bcol_idx, bsrm.values)
+        rc = dia        ? cgx_set_dia(ctx, diam.ndiag, diam.offsets, diam.data, n)
+             : bsr_bs > 0 ? cgx_set_bsr(ctx, (int)bsr_bs, bsrm.brow_ptr, bsrm.bcol_idx, bsrm.values)
              : csr_a32  ? cgx_set_csr_f32(ctx, csrm.row_ptr, csrm.col_idx, (const float *)csrm.values)
                         : cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, (const double *)csrm.values);
-        if (rc != CGX_OK) return die_cgx(rc, bsr_bs > 0 ? "cgx_set_bsr" : csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
+        if (rc != CGX_OK) return die_cgx(rc, dia ? "cgx_set_dia" : bsr_bs > 0 ? "cgx_set_bsr" : csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
         if (jacobi) { /* 1 / diag(A) from the uploaded matrix; a diagonal it refuses ends the run */
             rc = cgx_set_precond(ctx, CGX_PC_JACOBI);
             if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond");
@@ -767,6 +819,8 @@ int main(int argc, char **argv) {
         free(bsrm.brow_ptr);
         free(bsrm.bcol_idx);
         free(bsrm.values);
+        free(diam.offsets);
+        free(diam.data);
         if (rc != CGX_OK) return die_cgx(rc, "cgx_set_rows");
     } else if (stream_a) {
         /* A is on the device; b and x0 (MPI_Bcast / MPI_Scatter of the vectors) */
@@ -815,6 +869,7 @@ int main(int argc, char **argv) {
                st.rr >= 0 ? __builtin_sqrt(st.rr) : -1.0);
     if (stats && csr) printf("nnz: %lld\n", (long long)csrm.nnz);
     if (stats && bsr_bs > 0) printf("nnzb: %lld\n", (long long)bsrm.nnzb);
+    if (stats && dia) printf("ndiag: %lld\n", (long long)diam.ndiag);
     if (stats && csr_a32) printf("values: float\n");
     if (stats && jacobi) printf("precond: jacobi\n");
     if (stats && block_bs > 0) printf("precond: block-jacobi %lld\n", block_bs);

@@ -54,6 +54,17 @@ int csr_plan_args(int K, int R, int U, int nt) {
 }
 
 int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
+    if (c->dia) {  // diagonal-valued: 64 or 128 rows per wave, U diagonals in flight
+        if ((R != 64 && R != 128) || !spmv_dia_plan_ok(R / 64, U, nt))
+            return fail(CGX_ERR_ARG, "diagonal-valued cgx_create_csr context: rows_per_wave must be 64 or 128, "
+                                     "chunks_in_flight 1, 2, 4 or 8 and the load policy 2 or 8 (got %d, %d, %d)",
+                        R, U, nt);
+        Shard &s = c->sh[0];
+        TRY(set_dev(s));
+        s.plan = plan_spmv_dia(s.dev, s.nloc, c->dia_ndiag, R / 64, U, nt, blocks_per_cu);
+        c->csr_plan_user = true;
+        return CGX_OK;
+    }
     TRY(csr_plan_args(1, R, U, nt));
     for (auto &s : c->sh) {  // one T for every row block, each block's grid from its own rows
         TRY(set_dev(s));
@@ -178,7 +189,11 @@ static int pc_jacobi(cgx_ctx *c) {
         unsigned long long *pin = reinterpret_cast<unsigned long long *>(s.h_pin);
         pin[0] = ~0ull;
         HIPT(hipMemcpyAsync(slot(s, S_PCBAD), pin, 8, hipMemcpyHostToDevice, s.stream));
-        if (c->bsr_bs) {
+        if (c->dia) {
+            HIPT(dia_diag_minv_f64(c->n, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data),
+                                   c->dia_ld, f64(fresh), static_cast<unsigned long long *>(slot(s, S_PCBAD)),
+                                   s.stream));
+        } else if (c->bsr_bs) {
             HIPT(preload_kernels(PL_BSMV));
             HIPT(bsr_diag_minv_f64(c->n, c->bsr_bs, reinterpret_cast<const int64_t *>(s.csr_rp),
                                    reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(fresh),
@@ -391,6 +406,8 @@ static int csr_upload(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx
     const bool was_bsr = c->bsr_bs != 0;  // block-valued until now: a scalar context again (the tiled buffer stays)
     c->bsr_bs = 0;
     c->bsr_nnzb = 0;
+    if (c->dia) c->csr_plan_user = false;  // a diagonal plan counts rows per lane: it says nothing about T
+    c->dia = false;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
     if (!c->csr_plan_user) {
         if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs), 0, -1, 0, f32);
@@ -458,6 +475,7 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
         if (fresh) (void)hipFree(fresh);
         c->csr_nnz = -1;
         c->bsr_bs = 0;
+        c->dia = false;
         c->state = ST_IDLE;
         return rc;
     }
@@ -470,9 +488,70 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
     c->csr_f32 = false;
     c->bsr_bs = bs;
     c->bsr_nnzb = nnzb;
+    if (c->dia) c->csr_plan_user = false;  // a diagonal plan counts rows per lane: it says nothing about T
+    c->dia = false;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
     if (!c->csr_plan_user) s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs);
     else s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs, 64 / s.plan.R, s.plan.nt);  // the caller's T and policy
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
+// cgx_set_dia, after its checks: the offsets go into col_idx's place, the
+// diagonals at an even pitch (the 16-byte loads of two rows per lane) into the
+// context's values where they fit, otherwise into memory of the library's own,
+// which is allocated before the first byte moves, so a refusal leaves the
+// earlier matrix.
+static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld) {
+    Shard &s = c->sh[0];
+    const int64_t pitch = round_up(c->n, 2), need = ndiag * pitch;  // ndiag n <= csr_cap: no overflow
+    TRY(sync_all(c));  // iterations still enqueued read the arrays
+    TRY(set_dev(s));
+    HIPT(preload_kernels(PL_DIA));
+    char *fresh = nullptr;
+    if (need > c->csr_cap && need > s.dia_cap) {
+        const hipError_t e = hipMalloc(&fresh, (size_t)need * 8);
+        if (e != hipSuccess)
+            return fail(CGX_ERR_NOMEM, "hipMalloc(%zu bytes) on device %d: %s", (size_t)need * 8, s.dev,
+                        hipGetErrorString(e));
+    }
+    char *dst = need <= c->csr_cap ? s.csr_val : fresh ? fresh : s.dia_val;
+    const int rc = [&]() -> int {
+        if (ndiag > 0) {
+            HIPT(hipMemcpyAsync(s.csr_ci, offsets, (size_t)ndiag * 4, hipMemcpyHostToDevice, s.stream));
+            HIPT(hipMemcpy2DAsync(dst, (size_t)pitch * 8, data, (size_t)ld * 8, (size_t)c->n * 8, (size_t)ndiag,
+                                  hipMemcpyHostToDevice, s.stream));
+        }
+        HIPT(hipStreamSynchronize(s.stream));
+        return CGX_OK;
+    }();
+    if (rc != CGX_OK) {  // part of the new matrix is on the device: no matrix until the next cgx_set_csr / cgx_set_dia
+        if (fresh) (void)hipFree(fresh);
+        c->csr_nnz = -1;
+        c->bsr_bs = 0;
+        c->dia = false;
+        c->state = ST_IDLE;
+        return rc;
+    }
+    if (fresh) {
+        if (s.dia_val) HIPT(hipFree(s.dia_val));
+        s.dia_val = fresh;
+        s.dia_cap = need;
+    }
+    s.dia_data = dst;
+    const bool was_dia = c->dia;
+    c->csr_nnz = ndiag * c->n;
+    c->csr_f32 = false;
+    c->bsr_bs = 0;
+    c->bsr_nnzb = 0;
+    c->dia = true;
+    c->dia_ndiag = ndiag;
+    c->dia_ld = pitch;
+    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
+    if (c->csr_plan_user && was_dia)  // the caller's rows per lane, diagonals in flight and policy
+        s.plan = plan_spmv_dia(s.dev, s.nloc, ndiag, s.plan.R / 64, s.plan.U, s.plan.nt);
+    else
+        s.plan = plan_spmv_dia(s.dev, s.nloc, ndiag), c->csr_plan_user = false;
     c->state = ST_IDLE;
     return CGX_OK;
 }
@@ -578,7 +657,10 @@ int cgx_set_precond_block(cgx_ctx *c, int bs) {
     char *dD = nullptr;
     TRY(pc_alloc(s, (int64_t)cnt, &dD));
     auto extract = [&]() -> int {
-        if (c->bsr_bs)  // the same blocks from the BSR arrays, for any bs (cgx_bsmv.hip)
+        if (c->dia)  // the same blocks from the diagonals (cgx_dia.hip)
+            HIPT(dia_diag_blocks_f64(c->n, bs, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
+                                     f64(s.dia_data), c->dia_ld, f64(dD), s.stream));
+        else if (c->bsr_bs)  // the same blocks from the BSR arrays, for any bs (cgx_bsmv.hip)
             HIPT(bsr_diag_blocks_f64(c->n, c->bsr_bs, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
                                      reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(dD), s.stream));
         else
@@ -659,6 +741,16 @@ int cgx_csr_check(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t 
 int cgx_bsr_check(int64_t nb, int64_t nnzb, const int64_t *brow_ptr, const int32_t *bcol_idx) {
     return structure_check({"cgx_bsr_check", "nb", "nnzb", "brow_ptr", "bcol_idx", "block row"}, nb, nnzb, brow_ptr,
                            bcol_idx);
+}
+
+int cgx_dia_check(int64_t n, int64_t ndiag, const int32_t *offsets) {
+    if (n < 1 || ndiag < 0) return fail(CGX_ERR_ARG, "cgx_dia_check: n must be >= 1 and ndiag >= 0");
+    if (ndiag > 0 && !offsets) return fail(CGX_ERR_ARG, "cgx_dia_check: NULL pointer");
+    for (int64_t k = 0; k < ndiag; ++k)
+        if ((int64_t)offsets[k] <= -n || (int64_t)offsets[k] >= n)
+            return fail(CGX_ERR_SHAPE, "cgx_dia_check: offsets[%lld] = %d outside (-%lld, %lld)", (long long)k,
+                        (int)offsets[k], (long long)n, (long long)n);
+    return CGX_OK;
 }
 
 int cgx_csr_halo_counts(int64_t n, int nshards, const int64_t *row_ptr, const int32_t *col_idx, int64_t *counts) {
@@ -753,6 +845,45 @@ int cgx_set_bsr(cgx_ctx *c, int bs, const int64_t *brow_ptr, const int32_t *bcol
                     (long long)nnzb, bs, bs, (double)nnzb * (bs * bs), (long long)c->csr_cap);
     TRY(cgx_bsr_check(nb, nnzb, brow_ptr, bcol_idx));  // nothing is uploaded when it fails
     return bsr_upload(c, bs, nnzb, brow_ptr, bcol_idx, values);
+}
+
+int cgx_set_dia(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld) {
+    const Range range_("cgx_set_dia");
+    if (!c) return fail(CGX_ERR_ARG, "cgx_set_dia: ctx is NULL");
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_dia: not a cgx_create_csr context");
+    if (c->nr)
+        return fail(CGX_ERR_ARG, "cgx_set_dia: not with several right-hand sides (a cgx_create_csr_nrhs context): "
+                                 "batched DIA is not built");
+    if (c->csr_multi)
+        return fail(CGX_ERR_ARG, "cgx_set_dia: not over row blocks (a cgx_create_csr_multi context): DIA over row "
+                                 "blocks is not built");
+    if (ndiag < 0) return fail(CGX_ERR_ARG, "cgx_set_dia: ndiag must be >= 0 (got %lld)", (long long)ndiag);
+    if (ndiag > 0 && (!offsets || !data)) return fail(CGX_ERR_ARG, "cgx_set_dia: offsets / data is NULL");
+    if (ld < c->n)
+        return fail(CGX_ERR_SHAPE, "cgx_set_dia: ld = %lld is below n = %lld", (long long)ld, (long long)c->n);
+    if (ndiag > c->csr_cap / c->n)  // ndiag n > the room, without the product's overflow
+        return fail(CGX_ERR_SHAPE, "cgx_set_dia: %lld diagonals of %lld rows are %.0f entries, the context has room for "
+                                   "%lld", (long long)ndiag, (long long)c->n, (double)ndiag * (double)c->n,
+                    (long long)c->csr_cap);
+    TRY(cgx_dia_check(c->n, ndiag, offsets));  // nothing is uploaded when it fails
+    return dia_upload(c, ndiag, offsets, data, ld);
+}
+
+int cgx_spmv_dia(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld, const void *v,
+                 void *out, void *stream) {
+    if (n < 0 || ndiag < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia: bad shape");
+    if (ld < n) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia: ld = %lld is below n = %lld", (long long)ld, (long long)n);
+    if ((ndiag > 0 && (!offsets || !data)) || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_dia: NULL pointer");
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    RedWs ws;
+    TRY(dev_ws(&ws));
+    HIPT(preload_kernels(PL_DIA));
+    const MatvecPlan pl = plan_spmv_dia(dev, n, ndiag);  // the default rule unless CGX_DIA_PLAN names a plan
+    HIPT(spmv_dia_f64(pl, static_cast<const int32_t *>(offsets), static_cast<const double *>(data), ld, n, ndiag,
+                      static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
+                      static_cast<hipStream_t>(stream)));
+    return CGX_OK;
 }
 
 int cgx_bsr_tile_values(int64_t nnzb, int bs, const void *values, void *values_tiled, void *stream) {

@@ -4,7 +4,7 @@
 //   cgx_exchange.hip  the per-iteration exchanges (RCCL / device copies / p2p)
 //   cgx_iterate.hip   the conjugrad loop: begin, iterations, gating, solve
 //   cgx_nrhs.hip      cgx_create_nrhs / cgx_create_csr_nrhs contexts: several systems per pass over A
-//   cgx_csr.hip       cgx_create_csr / cgx_create_csr_multi contexts: A in CSR or block (BSR) storage (structure check, upload, the row blocks' exchange lists), diagonal and block preconditioning
+//   cgx_csr.hip       cgx_create_csr / cgx_create_csr_multi contexts: A in CSR, block (BSR) or diagonal (DIA) storage (structure check, upload, the row blocks' exchange lists), diagonal and block preconditioning
 //   cgx_pcblock.hip   block Jacobi's host side: the blocks' Cholesky inversion and the check of a caller's blocks
 //   cgx_api.hip       errors, devices and the kernel-level entry points
 // Not part of the C ABI (include/cgx.h).
@@ -196,6 +196,11 @@ struct Shard {
     // capacity, allocated by the first cgx_set_bsr that needs it and kept until the context goes
     char *bsr_val = nullptr;
     int64_t bsr_cap = 0;
+    // cgx_set_dia (cgx_ctx::dia): csr_ci holds the offsets (int32[ndiag]) and dia_data the diagonals at the pitch
+    // cgx_ctx::dia_ld -- csr_val where ndiag * dia_ld doubles fit the context's capacity, otherwise dia_val, dia_cap
+    // doubles of the library's own memory, allocated by the first cgx_set_dia that needs it (an odd n pads the pitch)
+    char *dia_val = nullptr, *dia_data = nullptr;
+    int64_t dia_cap = 0;
     // cgx_create_csr_multi: this block's rows only (row_ptr rebased to 0, col_idx still global), and its exchange
     // lists -- for every other block q the ascending offsets into q's slice that this block's col_idx names, source
     // after source in halo_idx (int32[halo_cap]), list q at halo.off[q] .. halo.off[q + 1]
@@ -313,6 +318,10 @@ struct cgx_ctx {
     // cgx_set_csr_f32 goes back to 0), and its stored blocks; csr_nnz is then bsr_nnzb * bsr_bs^2
     int bsr_bs = 0;
     int64_t bsr_nnzb = 0;
+    // cgx_set_dia: the context is diagonal-valued (until the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr), its
+    // diagonals and their device pitch (n rounded up to even); csr_nnz is then dia_ndiag * n
+    bool dia = false;
+    int64_t dia_ndiag = 0, dia_ld = 0;
     // cgx_create_csr_multi (whatever the block count): csr_cap is every block's room; halo_counts[d * S + q] =
     // the length of block d's list into block q (cgx_get_csr_halo); csr_halo: several blocks exchange p and x
     // through those lists (gather_indexed; false: whole slices, CGX_CSR_XCHG=full or CGX_LOCAL_XCHG=copy)

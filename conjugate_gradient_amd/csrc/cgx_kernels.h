@@ -87,6 +87,7 @@ struct MatvecPlan {
     int nrhs = 0;     // > 0: k_matvec_nrhs_f64's plan for this many vectors per pass (2, 4 or 8; nt is 2 or 8)
     int csr = 0;      // 1: k_csr_mult_f64's plan (R = 64 / T rows per wave, U = 1, nt is 2 or 8)
     int bsr = 0;      // > 0 (with csr = 1): k_bsr_mult_f64's plan for this block size (R = 64 / T block rows per wave)
+    int dia = 0;      // 1 (with csr = 1): k_dia_mult_f64's plan (R = 64 or 128 rows per wave, U diagonals in flight)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -263,6 +264,34 @@ hipError_t bsr_diag_minv_f64(int64_t n, int bs, const int64_t *brow_ptr, const i
                              double *minv, unsigned long long *bad, hipStream_t s);
 hipError_t bsr_diag_blocks_f64(int64_t n, int bs, int pbs, const int64_t *brow_ptr, const int32_t *bcol_idx,
                                const double *values, double *D, hipStream_t s);
+
+// ---- sparse A held by diagonals (cgx_dia.hip) --------------------------------------
+// out[i] = sum over k < ndiag with 0 <= i + offsets[k] < n, in stored order, of
+// data[k * ld + i + offsets[k]] * v[i + offsets[k]], one accumulator per row from
+// +0.0 (the order contract is in cgx_dia.hip); pown != nullptr: also *dot_out =
+// pown . out (fixed order for a fixed rows per wave and grid).  ld >= n; slots of
+// data that hold no entry of A are never read.  The offsets are not range-checked
+// here (cgx_dia_check), but an offset outside (-n, n) adds no term and reads nothing
+// outside the arrays.  The 16-byte loads of R = 2 are used when ld is even and data
+// and v are 16-byte aligned, 8-byte loads otherwise: the same bits.
+// The instantiated (R, U, policy): rows per lane R in {1, 2} (pl.R = 64 R), U in
+// {1, 2, 4, 8}, policy 2 or 8.
+bool spmv_dia_plan_ok(int R, int U, int nt);
+// R / U <= 0, nt < 0, blocks_per_cu <= 0 pick the defaults (env
+// CGX_DIA_PLAN="R=..,U=..,nt=..,bpc=.." may override with an instantiated plan; its R
+// counts rows per lane).  pl.csr = 1, pl.dia = 1.
+MatvecPlan plan_spmv_dia(int device, int64_t n, int64_t ndiag, int R = 0, int U = 0, int nt = -1,
+                         int blocks_per_cu = 0);
+hipError_t spmv_dia_f64(const MatvecPlan &pl, const int32_t *offsets, const double *data, int64_t ld, int64_t n,
+                        int64_t ndiag, const double *v, double *out, const double *pown, double *dot_out,
+                        const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
+// The preconditioners' one-time extraction from the diagonals, bit for bit what
+// csr_diag_minv_f64 / csr_diag_blocks_f64 (below) give on the expanded matrix -- row
+// i's entries diagonal after diagonal in stored order, in-range terms only.
+hipError_t dia_diag_minv_f64(int64_t n, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld,
+                             double *minv, unsigned long long *bad, hipStream_t s);
+hipError_t dia_diag_blocks_f64(int64_t n, int pbs, int64_t ndiag, const int32_t *offsets, const double *data,
+                               int64_t ld, double *D, hipStream_t s);
 
 // ---- several right-hand sides on a CSR matrix (cgx_spmm.hip) ----------------------
 // Out[j*ldo + i] = sum over row i's entries of values[e] * V[j*ldv + col_idx[e]]
@@ -519,16 +548,19 @@ hipError_t preload_spmm();
 hipError_t preload_pcg();
 hipError_t preload_pcg_block();
 hipError_t preload_bsmv();
+hipError_t preload_dia();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
-    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512, PL_PCG_BLOCK = 1024, PL_BSMV = 2048
+    PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512, PL_PCG_BLOCK = 1024, PL_BSMV = 2048,
+    PL_DIA = 4096
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
         {PL_MATVEC, preload_matvec}, {PL_VECTOR, preload_vector}, {PL_POISSON, preload_poisson},
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
         {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg},
-        {PL_SPMM, preload_spmm}, {PL_PCG_BLOCK, preload_pcg_block}, {PL_BSMV, preload_bsmv}};
+        {PL_SPMM, preload_spmm}, {PL_PCG_BLOCK, preload_pcg_block}, {PL_BSMV, preload_bsmv},
+        {PL_DIA, preload_dia}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

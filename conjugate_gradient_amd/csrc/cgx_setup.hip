@@ -232,7 +232,7 @@ void free_shard(Shard &s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm) ncclCommDestroy(s.comm);
     for (char *p : {s.A, s.b, s.x, s.rh ? s.rh : s.r, s.p2, s.p3, s.Ap, s.pfull, s.p_alt, s.xfull, s.scal, s.sym_prow,
-                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.bsr_val, s.halo_idx, s.pc_minv, s.pc_w,
+                    s.sym_pcol, s.sym_stage, s.csr_rp, s.csr_ci, s.csr_val, s.bsr_val, s.dia_val, s.halo_idx, s.pc_minv, s.pc_w,
                     s.pc_z})
         if (p) (void)hipFree(p);
     if (s.ws.partials) (void)hipFree(s.ws.partials);
@@ -868,6 +868,7 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
         info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0) |
                        (c->csr_f32 ? CGX_A_F32 : 0) |  // float-valued since cgx_set_csr_f32
                        (c->bsr_bs ? CGX_BSR_ACTIVE : 0) |  // block-valued since cgx_set_bsr
+                       (c->dia ? CGX_DIA_ACTIVE : 0) |  // diagonal-valued since cgx_set_dia
                        (c->csr_halo ? CGX_CSR_HALO_ACTIVE : 0);
     info->elem_bytes = c->es;
     return CGX_OK;

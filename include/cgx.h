@@ -389,6 +389,67 @@
  *       stored order, j ascending inside a block); the failures are CSR's.
  *     - Not built: float-stored BSR values, several right-hand sides, several
  *       row blocks, bs = 1, a rectangular block shape.
+ *   - Diagonal storage (cgx_set_dia, on a plain cgx_create_csr context):
+ *     structured grids with variable coefficients, 5-, 7- and 27-point stencils
+ *     and banded systems are a handful of diagonals.  Held by diagonals a matrix
+ *     has no column indices and no gathers: an entry streams 8 bytes in place
+ *     of CSR's 12, a row 8 ndiag + 16 in place of 12 L + 24.
+ *     - Storage (scipy's dia_matrix, square): offsets is int32_t[ndiag], data
+ *       double[ndiag * ld] with ld >= n; data[k * ld + j] is
+ *       A[j - offsets[k]][j] -- the slot is indexed by the column.  Row i reads
+ *       data[k * ld + i + o] and v[i + o], o = offsets[k], where
+ *       0 <= i + o < n.  Slots outside that range are never read, on the host
+ *       or on the device, and may hold NaN.  Diagonals are taken in stored
+ *       order and need not be sorted, a duplicate offset is two terms, a stored
+ *       zero is a term.  ndiag = 0 is the zero matrix (the pointers may be
+ *       NULL).
+ *     - Summation order (k_dia_mult_f64).  Row i starts from +0.0 and, for
+ *       k = 0 .. ndiag-1 in stored order where 0 <= i + offsets[k] < n, does
+ *       acc = fma(data[k][i + o], v[i + o], acc): one accumulator per row, no
+ *       cross-lane combine.  A row's sum depends on nothing but the matrix and
+ *       v -- not on the rows per lane, the diagonals in flight, the load
+ *       policy, the grid or the device pitch; a row no diagonal reaches gives
+ *       +0.0.  The fused p.Ap goes the CSR kernel's way; deterministic for a
+ *       given rows per lane and grid.
+ *     - cgx_dia_check (host only): n < 1, ndiag < 0 or NULL offsets with
+ *       ndiag > 0 is CGX_ERR_ARG; an offset <= -n or >= n is CGX_ERR_SHAPE,
+ *       the first such k and its value named.
+ *     - cgx_set_dia checks, in this order: a NULL context (CGX_ERR_ARG); not a
+ *       plain cgx_create_csr context -- cgx_create_csr_nrhs and
+ *       cgx_create_csr_multi included, batched and row-block DIA are not built
+ *       (CGX_ERR_ARG); ndiag < 0, or NULL offsets / data with ndiag > 0
+ *       (CGX_ERR_ARG); ld < n (CGX_ERR_SHAPE); ndiag n above the creation-time
+ *       nnz (CGX_ERR_SHAPE, both counts named; the padding of the device pitch
+ *       is not charged); cgx_dia_check.  Nothing is uploaded when one fails:
+ *       the earlier matrix (CSR, BSR or DIA), its value type, its plan and its
+ *       preconditioner stay, and a later solve gives the bits it gave before.
+ *     - A successful call ends a solve in progress, turns preconditioning off,
+ *       makes a new default plan unless the caller chose one on a
+ *       diagonal-valued context already, and makes the context diagonal-valued
+ *       until the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr, after which
+ *       the context gives a fresh context's bits again (and a default plan).
+ *       cgx_get_info: flags carries CGX_DIA_ACTIVE | CGX_CSR_ACTIVE, never
+ *       CGX_BSR_ACTIVE with it.  On the device the diagonals lie at an even
+ *       pitch, in the context's own values where they fit and otherwise (an
+ *       odd n at full capacity) in memory of the library's own.
+ *     - cgx_set_matvec_plan: rows_per_wave = 64 R in {64, 128} (R rows per
+ *       lane), chunks_in_flight = U in {1, 2, 4, 8} diagonals in flight, load
+ *       policy 2 or 8; anything else is CGX_ERR_ARG and the plan stays.
+ *       The default is R = 1, U = 1, policy 8 (measured at 5 and 65 diagonals,
+ *       DESIGN.md s3); CGX_DIA_PLAN="R=..,U=..,nt=..,bpc=.." (R = 1 or 2)
+ *       overrides it.
+ *     - The iteration is untouched: the three-launch one in every host form,
+ *       x the same bits across them for a given plan; only the matVec (and
+ *       cgx_residual_norm's) is the diagonal kernel.
+ *     - Preconditioners: cgx_set_precond_diag and
+ *       cgx_set_precond_block_values never read the matrix.  CGX_PC_JACOBI and
+ *       cgx_set_precond_block(pbs), any pbs in 2..8, extract from the
+ *       diagonals and give, bit for bit, the 1 / diag(A) and the diagonal
+ *       blocks a double-valued CSR context gives on the expanded matrix (row
+ *       i's entries listed diagonal after diagonal in stored order, in-range
+ *       terms only, stored zeros included); the failures are CSR's.
+ *     - Not built: float-stored diagonals, several right-hand sides, several
+ *       row blocks, one-sided storage of a symmetric A, rectangular matrices.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -422,7 +483,8 @@ extern "C" {
                            cgx_create_csr_multi, cgx_csr_halo_counts, cgx_csr_halo_list,
                            cgx_get_csr_halo and cgx_gather_indexed, and the reported bit
                            CGX_CSR_HALO_ACTIVE; likewise cgx_set_bsr, cgx_bsr_check, cgx_spmv_bsr and
-                           cgx_bsr_tile_values, and the reported bit CGX_BSR_ACTIVE */
+                           cgx_bsr_tile_values, and the reported bit CGX_BSR_ACTIVE; likewise cgx_set_dia,
+                           cgx_dia_check and cgx_spmv_dia, and the reported bit CGX_DIA_ACTIVE */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -438,6 +500,8 @@ extern "C" {
 #define CGX_F64          0x0   /* double data (default)                        */
 #define CGX_F32_REF      0x1   /* float data, bit-exact serialConjugate.c order */
 #define CGX_A_F32        0x2   /* float A, double vectors and arithmetic (above) */
+#define CGX_DIA_ACTIVE   0x4   /* reported in cgx_info.flags: a cgx_create_csr context that is
+                                  diagonal-valued (cgx_set_dia), beside CGX_CSR_ACTIVE */
 #define CGX_TIMING       0x100 /* time every matVec launch with HIP events      */
 #define CGX_NO_OVERLAP   0x400 /* multi-shard dense fp64: do not overlap the p
                                   exchange with the own-column-block matVec
@@ -768,6 +832,14 @@ int cgx_bsr_check(int64_t nb, int64_t nnzb, const int64_t *brow_ptr, const int32
  * the context's nnz), 2 <= bs <= CGX_MAX_BSR_BLOCK; makes a plain cgx_create_csr context block-valued
  * until the next cgx_set_csr / cgx_set_csr_f32.  Checks and effects: "Block storage" above. */
 int cgx_set_bsr(cgx_ctx *ctx, int bs, const int64_t *brow_ptr, const int32_t *bcol_idx, const double *values);
+/* ---- diagonal (DIA) storage on a cgx_create_csr context (see "Diagonal storage" above) ---- */
+/* Host-only: n >= 1, ndiag >= 0, every offset inside (-n, n) -- CGX_ERR_SHAPE names the first
+ * offsets[k] outside and its value. */
+int cgx_dia_check(int64_t n, int64_t ndiag, const int32_t *offsets);
+/* Host arrays in scipy's dia_matrix layout (data[k * ld + j] = A[j - offsets[k]][j], ld >= n,
+ * ndiag * n at most the context's nnz); makes a plain cgx_create_csr context diagonal-valued until
+ * the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr.  Checks and effects: "Diagonal storage" above. */
+int cgx_set_dia(cgx_ctx *ctx, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld);
 /* One GPU, fp64: nrhs (1..CGX_MAX_NRHS) systems A x_j = b_j on one CSR matrix with room for
  * nnz entries, solved together, one read of the CSR arrays per iteration.
  * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
@@ -954,6 +1026,14 @@ int cgx_bsr_tile_values(int64_t nnzb, int bs, const void *values, void *values_t
  * range-check them.  T comes from CGX_BSMV_PLAN="T=..,nt=..,bpc=.." (default T = 8). */
 int cgx_spmv_bsr(int64_t nb, int64_t ncolb, int bs, const void *brow_ptr, const void *bcol_idx,
                  const void *values_tiled, const void *v, void *out, void *stream);
+/* Kernel-level, device pointers: out[i] = sum over k < ndiag with 0 <= i + offsets[k] < n of
+ * data[k*ld + i + offsets[k]] * v[i + offsets[k]], i < n, in the order of "Diagonal storage" above;
+ * offsets is int32[ndiag], data double[ndiag * ld], ld >= n.  An even ld with 16-byte aligned data
+ * and v lets two rows per lane use 16-byte loads; the bits do not depend on it.  The offsets should
+ * have passed cgx_dia_check; one outside (-n, n) adds no term.  The plan comes from
+ * CGX_DIA_PLAN="R=..,U=..,nt=..,bpc=.." (default: the context's rule). */
+int cgx_spmv_dia(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld,
+                 const void *v, void *out, void *stream);
 /* Kernel-level, device pointers: Out[j*ldo + i] = sum_e values[e] * V[j*ldv + col_idx[e]],
  * j < nrhs.  Column j is cgx_spmv_csr's result on column j bit for bit at the same T.
  * The indices must have passed cgx_csr_check.  T comes from
