@@ -41,6 +41,7 @@ __all__ = [
     "CGX_CSR_ACTIVE", "spmv_csr", "spmm_csr",
     "CGX_BSR_ACTIVE", "CGX_MAX_BSR_BLOCK", "bsr_check", "spmv_bsr",
     "CGX_DIA_ACTIVE", "dia_check", "spmv_dia",
+    "CGX_DIA_SYM_ACTIVE", "dia_sym_check", "spmv_dia_sym",
     "CGX_CSR_HALO_ACTIVE", "csr_halo_counts", "csr_halo_list", "gather_indexed",
     "CGX_PRECOND_ACTIVE", "PRECOND_KINDS", "PC_BLOCK", "CGX_MAX_PC_BLOCK", "csr_diag_blocks", "precond_block_invert",
     "conjugrad", "matVec", "vecVec", "residual", "update_xr", "update_p", "read_text",
@@ -76,6 +77,7 @@ CGX_CSR_HALO_ACTIVE = 0x20000000
 CGX_BSR_ACTIVE = 0x40000000  # reported in info.flags beside CGX_CSR_ACTIVE: a CSR solver that is block-valued (set_bsr)
 CGX_MAX_BSR_BLOCK = 8  # the largest block size of set_bsr
 CGX_DIA_ACTIVE = 0x4  # reported in info.flags beside CGX_CSR_ACTIVE: a CSR solver that is diagonal-valued (set_dia)
+CGX_DIA_SYM_ACTIVE = 0x8  # ... beside CGX_DIA_ACTIVE: the upper diagonals of a symmetric A alone (set_dia_sym)
 # cgx_set_precond's kinds, CGX_PC_NONE / CGX_PC_JACOBI / CGX_PC_DIAG (include/cgx.h), by the names Solver.precond
 # reports.  Kept out of the CGX_* names: those are the flag words, and a kind is not a bit of one.
 PRECOND_KINDS = {"none": 0, "jacobi": 1, "diag": 2}
@@ -202,6 +204,9 @@ def lib() -> ctypes.CDLL:
         "cgx_dia_check": ([i64, i64, vp], i32),
         "cgx_set_dia": ([vp, i64, vp, vp, i64], i32),
         "cgx_spmv_dia": ([i64, i64, vp, vp, i64, vp, vp, vp], i32),
+        "cgx_dia_sym_check": ([i64, i64, vp], i32),
+        "cgx_set_dia_sym": ([vp, i64, vp, vp, i64], i32),
+        "cgx_spmv_dia_sym": ([i64, i64, vp, vp, i64, vp, vp, vp], i32),
         "cgx_spmv_csr_f32": ([i64, i64, vp, vp, vp, vp, vp, vp], i32),
         "cgx_create_csr_nrhs": ([pctx, i64, i64, i32, i32, i32], i32),
         "cgx_create_csr_multi": ([pctx, i64, i64, i32, ctypes.POINTER(i32), i32], i32),
@@ -608,6 +613,45 @@ def spmv_dia(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> None:
     d_d = DeviceArray.from_host(d.reshape(-1) if ndiag else np.zeros(1))
     try:
         _check(L.cgx_spmv_dia(int(n), ndiag, d_o.ptr, d_d.ptr, ld, v.ptr, out.ptr, None), "cgx_spmv_dia")
+        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
+    finally:
+        for a in (d_o, d_d):
+            a.free()
+
+
+def dia_sym_check(offsets, n: int) -> None:
+    """cgx_dia_sym_check (host only, no GPU): raises CgxError(-4) naming the first offset outside [0, n) -- one-sided
+    storage holds offsets >= 0, the diagonal -o is the stored diagonal o."""
+    o = np.asarray(offsets)
+    _need(o.ndim == 1 and (o.dtype.kind in "iu" or o.size == 0), "dia_sym_check: offsets are one-dimensional integers")
+    _need(isinstance(n, (int, np.integer)), "dia_sym_check: n is an integer")
+    _need(o.size == 0 or (int(o.min()) >= -2**31 and int(o.max()) < 2**31),
+          "dia_sym_check: an offset does not fit int32")
+    o = np.ascontiguousarray(o, np.int32)
+    _check(lib().cgx_dia_sym_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_sym_check")
+
+
+def spmv_dia_sym(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> None:
+    """out = A v for the symmetric A whose upper diagonals ``offsets`` (>= 0) / ``data`` hold, scipy's dia_matrix
+    layout of triu(A): per stored diagonal k, in stored order, ``data[k, i + o] * v[i + o]`` where o > 0 and
+    i + o < n, then ``data[k, i] * v[i - o]`` where i - o >= 0 (k_dia_sym_mult_f64; the plan from CGX_DIA_SYM_PLAN)
+    -- the bits of :func:`spmv_dia` on the expansion (o, then -o).  ``data`` has shape (ndiag, ld), ld >= n.  The
+    offsets come as a host array: they are checked (cgx_dia_sym_check) and only then uploaded; slots outside
+    [o, n) are never read by the kernel."""
+    o, d = _dia_arrays("spmv_dia_sym", offsets, data)
+    _need(isinstance(n, (int, np.integer)) and n >= 1, "spmv_dia_sym: need an integer n >= 1")
+    ld = int(d.shape[1])
+    _need(ld >= n, f"spmv_dia_sym: data has {ld} columns, n = {n} needed")
+    _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_dia_sym: float64 only")
+    _fits([v], n, "spmv_dia_sym v")
+    _fits([out], n, "spmv_dia_sym out")
+    L = lib()
+    _check(L.cgx_dia_sym_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_sym_check")
+    ndiag = int(o.size)
+    d_o = DeviceArray.from_host(o if ndiag else np.zeros(1, np.int32))
+    d_d = DeviceArray.from_host(d.reshape(-1) if ndiag else np.zeros(1))
+    try:
+        _check(L.cgx_spmv_dia_sym(int(n), ndiag, d_o.ptr, d_d.ptr, ld, v.ptr, out.ptr, None), "cgx_spmv_dia_sym")
         _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
     finally:
         for a in (d_o, d_d):
@@ -1043,6 +1087,50 @@ class Solver:
               f"{self.csr_nnz}")
         _check(lib().cgx_set_dia(self._h, int(o.size), _ptr(o) if o.size else None, _ptr(d) if o.size else None,
                                  int(d.shape[1])), "cgx_set_dia")
+
+    @classmethod
+    def from_dia_sym(cls, offsets, data=None, *, n: int | None = None, precond=None, device: int = 0,
+                     flags: int = CGX_F64) -> "Solver":
+        """A CSR solver sized for this symmetric matrix held by its upper diagonals (room for ndiag * n entries, the
+        stored count), with the matrix set through :meth:`set_dia_sym` (b = 0, x0 = 0) and, with ``precond``, its
+        preconditioner (:meth:`set_precond`).  Arguments as :meth:`from_dia`'s."""
+        if n is None and data is None and hasattr(offsets, "shape") and hasattr(offsets, "offsets"):
+            n = int(offsets.shape[0])
+        o, d = _dia_arrays("from_dia_sym", offsets, data)
+        n = int(d.shape[1]) if n is None else n
+        _need(isinstance(n, (int, np.integer)) and n >= 1, f"from_dia_sym: n must be an integer >= 1 (got {n})")
+        _need(d.shape[1] >= n, f"from_dia_sym: data has {d.shape[1]} columns, n = {n} needed")
+        s = cls.csr(int(n), int(o.size) * int(n), device=device, flags=flags)
+        try:
+            s.set_dia_sym(o, d)
+            if precond is not None:
+                s.set_precond(precond)
+        except Exception:
+            s.close()
+            raise
+        return s
+
+    def set_dia_sym(self, offsets, data=None) -> None:
+        """cgx_set_dia_sym: the symmetric matrix of a ``csr_nnz`` solver held by the diagonals of its upper triangle,
+        scipy's dia_matrix layout of triu(A) (offsets >= 0, ``data`` of shape (ndiag, ld), ld >= n,
+        ``data[k, j] = A[j - offsets[k], j]`` for j in [offsets[k], n); or one object with ``.offsets / .data``).  The
+        stored diagonal o > 0 also stands for the diagonal -o; the one-sided kernel k_dia_sym_mult_f64 reads each
+        value once for both.  Symmetry cannot be checked: only one triangle is given.  Slots outside
+        [offsets[k], n) are never read and may hold NaN.  The offsets are checked before anything is uploaded:
+        CgxError(-4) names the first offence and the earlier matrix stays.  The solver is one-sided
+        (``info().flags`` carries CGX_DIA_SYM_ACTIVE | CGX_DIA_ACTIVE) until the next :meth:`set_csr` /
+        :meth:`set_bsr` / :meth:`set_dia`; preconditioning is off afterwards.  One GPU, one right-hand side,
+        float64 values."""
+        _need(getattr(self, "csr_nnz", None) is not None, "set_dia_sym: the solver was not created with csr_nnz=")
+        _need(getattr(self, "devices", None) is None and getattr(self, "nrhs", None) is None,
+              "set_dia_sym: diagonal storage runs on one GPU with one right-hand side (not with devices= or nrhs=)")
+        o, d = _dia_arrays("set_dia_sym", offsets, data)
+        _need(d.shape[1] >= self.n, f"set_dia_sym: data has {d.shape[1]} columns, n = {self.n} needed")
+        _need(o.size * self.n <= self.csr_nnz,
+              f"set_dia_sym: {o.size} stored diagonals of {self.n} rows are {o.size * self.n} entries, the solver has "
+              f"room for {self.csr_nnz}")
+        _check(lib().cgx_set_dia_sym(self._h, int(o.size), _ptr(o) if o.size else None,
+                                     _ptr(d) if o.size else None, int(d.shape[1])), "cgx_set_dia_sym")
 
     def csr_halo(self) -> np.ndarray:
         """cgx_get_csr_halo: the ``(nshards, nshards)`` exchange counts in use on a CSR solver over row blocks

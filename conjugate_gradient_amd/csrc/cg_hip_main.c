@@ -57,7 +57,13 @@
  * whole, offsets ascending, zero-filled, and the solve runs through
  * cgx_set_dia and the gather-free diagonal kernel; takes --jacobi or
  * --block-jacobi as --csr does, not --csr-a32 or --bsr; --stats adds
- * "ndiag: <count>").
+ * "ndiag: <count>"),
+ * --dia-sym (with --csr: the matrix laid out as --dia does, then checked for
+ * A[i][j] == A[j][i] slot for slot -- the first (i, j) that differs ends the
+ * run -- and only the diagonals of offset >= 0 kept; the solve runs through
+ * cgx_set_dia_sym and the one-sided diagonal kernel, each stored value read
+ * once for both triangles; options and output as --dia's, "ndiag: <count>" the
+ * stored count; not with --csr-a32, --bsr or --dia).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -147,8 +153,10 @@ static void usage(const char *prog) {
             "       %s --csr --bsr BS [--jacobi | --block-jacobi BS] ... (--csr held as dense BS x BS blocks, BS in 2..8\n"
             "          dividing N, multiplied by the block kernel; not with --csr-a32)\n"
             "       %s --csr --dia [--jacobi | --block-jacobi BS] ... (--csr held as the diagonals that hold an entry,\n"
-            "          multiplied by the diagonal kernel; not with --csr-a32 or --bsr)\n",
-            prog, prog, prog, prog, prog, prog, prog);
+            "          multiplied by the diagonal kernel; not with --csr-a32 or --bsr)\n"
+            "       %s --csr --dia-sym [--jacobi | --block-jacobi BS] ... (--csr, symmetric, held as the diagonals of its\n"
+            "          upper triangle alone, multiplied by the one-sided diagonal kernel; not with --csr-a32, --bsr or --dia)\n",
+            prog, prog, prog, prog, prog, prog, prog, prog);
 }
 
 static int die_cgx(int rc, const char *what) {
@@ -429,6 +437,33 @@ static int dia_from_csr(const csr_host *m, int64_t n, dia_host *out) {
     return 0;
 }
 
+/* --dia-sym: the diagonals of dia_from_csr checked for symmetry -- diagonal -o
+ * must equal diagonal +o slot for slot, a diagonal the matrix lacks being +0.0
+ * -- and cut down in place to the offsets >= 0, still ascending.  Returns 0, or
+ * -1 with the first (i, j) in row order where A[i][j] != A[j][i]. */
+static int dia_sym_from_dia(dia_host *m, int64_t n, int64_t *bad_i, int64_t *bad_j) {
+    int64_t k0 = 0; /* the first diagonal of offset >= 0 */
+    while (k0 < m->ndiag && m->offsets[k0] < 0) ++k0;
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t k = 0; k < m->ndiag; ++k) {
+            const int64_t o = m->offsets[k], j = i + o;
+            if (o == 0 || j < 0 || j >= n) continue;
+            int64_t km = -1; /* the diagonal -o, if the matrix has it */
+            for (int64_t q = 0; q < m->ndiag; ++q)
+                if (m->offsets[q] == -o) km = q;
+            const double a = m->data[k * n + j], at = km >= 0 ? m->data[km * n + i] : 0.0; /* A[i][j], A[j][i] */
+            if (a != at) {
+                *bad_i = i;
+                *bad_j = j;
+                return -1;
+            }
+        }
+    for (int64_t k = k0; k < m->ndiag; ++k) m->offsets[k - k0] = m->offsets[k];
+    if (k0 > 0 && m->ndiag > k0) memmove(m->data, m->data + k0 * n, (size_t)(m->ndiag - k0) * (size_t)n * sizeof(double));
+    m->ndiag -= k0;
+    return 0;
+}
+
 /* Whole-string numeric option values: "--eps abc" or "--gpus 2x" is an
  * error (exit 2), not a silent 0. */
 static int opt_ll(const char *name, const char *v, long long *out) {
@@ -458,6 +493,7 @@ int main(int argc, char **argv) {
     long long max_iter = -1, n_opt = -1, spd_n = -1, nrhs = 0, block_bs = 0; /* block_bs > 0: --block-jacobi */
     long long bsr_bs = 0; /* > 0: --bsr */
     int dia = 0;          /* --dia */
+    int dia_sym = 0;      /* --dia-sym: becomes dia = 1 once the combinations are checked */
     unsigned long long seed = 42;
     const char *dims_path = NULL;
     const char *pos[3];
@@ -490,6 +526,7 @@ int main(int argc, char **argv) {
                 return 2;
             }
         } else if (!strcmp(a, "--dia")) dia = 1;
+        else if (!strcmp(a, "--dia-sym")) dia_sym = 1;
         else if (!strcmp(a, "--eps") && has_val) {
             if (!opt_double(a, argv[++i], &eps)) return 2;
         } else if (!strcmp(a, "--max-iter") && has_val) {
@@ -526,6 +563,11 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--csr-a32 is --csr with float-stored values: it is given alone (no --csr, --fp32-ref, --a-fp32, --symmetric, --gpus, --p2p, --nrhs, --spd)\n");
         return 2;
     }
+    if (dia_sym && (csr_a32 || bsr_bs > 0 || dia || !csr)) {
+        fprintf(stderr, "--dia-sym holds a --csr matrix by its upper diagonals, double values: it is given with --csr (not --csr-a32, --bsr or --dia)\n");
+        return 2;
+    }
+    if (dia_sym) dia = 1; /* laid out by diagonals first */
     if (bsr_bs > 0 && (csr_a32 || !csr)) {
         fprintf(stderr, "--bsr holds a --csr matrix as dense blocks of double values: it is given with --csr (not --csr-a32)\n");
         return 2;
@@ -690,6 +732,12 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "can't allocate memory for vector\n");
                 read_rc = -9;
             }
+            int64_t bi = 0, bj = 0;
+            if (!read_rc && dia_sym && dia_sym_from_dia(&diam, n, &bi, &bj) != 0) {
+                fprintf(stderr, "--dia-sym: the matrix is not symmetric: A[i][j] != A[j][i] first at (%lld, %lld), "
+                                "mirrored at (%lld, %lld)\n", (long long)bi, (long long)bj, (long long)bj, (long long)bi);
+                read_rc = -4;
+            }
         }
         t_parsed = now_s();
         if (threaded) pthread_join(creator, NULL); /* before any exit: HIP may be starting up on it */
@@ -797,11 +845,12 @@ int main(int argc, char **argv) {
         t_dist1 = now_s();
         if (rc != CGX_OK) return die_cgx(rc, "cgx_generate_spd");
     } else if (csr) {
-        rc = dia        ? cgx_set_dia(ctx, diam.ndiag, diam.offsets, diam.data, n)
+        rc = dia_sym    ? cgx_set_dia_sym(ctx, diam.ndiag, diam.offsets, diam.data, n)
+             : dia      ? cgx_set_dia(ctx, diam.ndiag, diam.offsets, diam.data, n)
              : bsr_bs > 0 ? cgx_set_bsr(ctx, (int)bsr_bs, bsrm.brow_ptr, bsrm.bcol_idx, bsrm.values)
              : csr_a32  ? cgx_set_csr_f32(ctx, csrm.row_ptr, csrm.col_idx, (const float *)csrm.values)
                         : cgx_set_csr(ctx, csrm.row_ptr, csrm.col_idx, (const double *)csrm.values);
-        if (rc != CGX_OK) return die_cgx(rc, dia ? "cgx_set_dia" : bsr_bs > 0 ? "cgx_set_bsr" : csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
+        if (rc != CGX_OK) return die_cgx(rc, dia_sym ? "cgx_set_dia_sym" : dia ? "cgx_set_dia" : bsr_bs > 0 ? "cgx_set_bsr" : csr_a32 ? "cgx_set_csr_f32" : "cgx_set_csr");
         if (jacobi) { /* 1 / diag(A) from the uploaded matrix; a diagonal it refuses ends the run */
             rc = cgx_set_precond(ctx, CGX_PC_JACOBI);
             if (rc != CGX_OK) return die_cgx(rc, "cgx_set_precond");

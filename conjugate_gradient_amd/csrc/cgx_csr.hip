@@ -54,6 +54,17 @@ int csr_plan_args(int K, int R, int U, int nt) {
 }
 
 int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
+    if (c->dia && c->dia_sym) {  // one-sided: the diagonal kernel's ranges, U stored diagonals in flight
+        if ((R != 64 && R != 128) || !spmv_dia_sym_plan_ok(R / 64, U, nt))
+            return fail(CGX_ERR_ARG, "one-sided diagonal-valued cgx_create_csr context: rows_per_wave must be 64 or "
+                                     "128, chunks_in_flight 1, 2, 4 or 8 and the load policy 2 or 8 (got %d, %d, %d)",
+                        R, U, nt);
+        Shard &s = c->sh[0];
+        TRY(set_dev(s));
+        s.plan = plan_spmv_dia_sym(s.dev, s.nloc, c->dia_ndiag, R / 64, U, nt, blocks_per_cu);
+        c->csr_plan_user = true;
+        return CGX_OK;
+    }
     if (c->dia) {  // diagonal-valued: 64 or 128 rows per wave, U diagonals in flight
         if ((R != 64 && R != 128) || !spmv_dia_plan_ok(R / 64, U, nt))
             return fail(CGX_ERR_ARG, "diagonal-valued cgx_create_csr context: rows_per_wave must be 64 or 128, "
@@ -407,7 +418,7 @@ static int csr_upload(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx
     c->bsr_bs = 0;
     c->bsr_nnzb = 0;
     if (c->dia) c->csr_plan_user = false;  // a diagonal plan counts rows per lane: it says nothing about T
-    c->dia = false;
+    c->dia = c->dia_sym = false;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
     if (!c->csr_plan_user) {
         if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs), 0, -1, 0, f32);
@@ -475,7 +486,7 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
         if (fresh) (void)hipFree(fresh);
         c->csr_nnz = -1;
         c->bsr_bs = 0;
-        c->dia = false;
+        c->dia = c->dia_sym = false;
         c->state = ST_IDLE;
         return rc;
     }
@@ -489,7 +500,7 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
     c->bsr_bs = bs;
     c->bsr_nnzb = nnzb;
     if (c->dia) c->csr_plan_user = false;  // a diagonal plan counts rows per lane: it says nothing about T
-    c->dia = false;
+    c->dia = c->dia_sym = false;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
     if (!c->csr_plan_user) s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs);
     else s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs, 64 / s.plan.R, s.plan.nt);  // the caller's T and policy
@@ -501,13 +512,13 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
 // diagonals at an even pitch (the 16-byte loads of two rows per lane) into the
 // context's values where they fit, otherwise into memory of the library's own,
 // which is allocated before the first byte moves, so a refusal leaves the
-// earlier matrix.
-static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld) {
+// earlier matrix.  sym: cgx_set_dia_sym, the same arrays read as the upper diagonals.
+static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld, bool sym) {
     Shard &s = c->sh[0];
     const int64_t pitch = round_up(c->n, 2), need = ndiag * pitch;  // ndiag n <= csr_cap: no overflow
     TRY(sync_all(c));  // iterations still enqueued read the arrays
     TRY(set_dev(s));
-    HIPT(preload_kernels(PL_DIA));
+    HIPT(preload_kernels(sym ? PL_DIA | PL_DIA_SYM : PL_DIA));  // CGX_PC_JACOBI's extraction is the diagonal file's
     char *fresh = nullptr;
     if (need > c->csr_cap && need > s.dia_cap) {
         const hipError_t e = hipMalloc(&fresh, (size_t)need * 8);
@@ -529,7 +540,7 @@ static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const d
         if (fresh) (void)hipFree(fresh);
         c->csr_nnz = -1;
         c->bsr_bs = 0;
-        c->dia = false;
+        c->dia = c->dia_sym = false;
         c->state = ST_IDLE;
         return rc;
     }
@@ -539,19 +550,21 @@ static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const d
         s.dia_cap = need;
     }
     s.dia_data = dst;
-    const bool was_dia = c->dia;
+    const bool same_kind = c->dia && c->dia_sym == sym;  // a plan chosen on the other kind names another kernel's
     c->csr_nnz = ndiag * c->n;
     c->csr_f32 = false;
     c->bsr_bs = 0;
     c->bsr_nnzb = 0;
     c->dia = true;
+    c->dia_sym = sym;
     c->dia_ndiag = ndiag;
     c->dia_ld = pitch;
     TRY(pc_drop(c));  // the diagonal belonged to the old matrix
-    if (c->csr_plan_user && was_dia)  // the caller's rows per lane, diagonals in flight and policy
-        s.plan = plan_spmv_dia(s.dev, s.nloc, ndiag, s.plan.R / 64, s.plan.U, s.plan.nt);
+    const auto plan = sym ? plan_spmv_dia_sym : plan_spmv_dia;
+    if (c->csr_plan_user && same_kind)  // the caller's rows per lane, diagonals in flight and policy
+        s.plan = plan(s.dev, s.nloc, ndiag, s.plan.R / 64, s.plan.U, s.plan.nt, 0);
     else
-        s.plan = plan_spmv_dia(s.dev, s.nloc, ndiag), c->csr_plan_user = false;
+        s.plan = plan(s.dev, s.nloc, ndiag, 0, 0, -1, 0), c->csr_plan_user = false;
     c->state = ST_IDLE;
     return CGX_OK;
 }
@@ -657,7 +670,10 @@ int cgx_set_precond_block(cgx_ctx *c, int bs) {
     char *dD = nullptr;
     TRY(pc_alloc(s, (int64_t)cnt, &dD));
     auto extract = [&]() -> int {
-        if (c->dia)  // the same blocks from the diagonals (cgx_dia.hip)
+        if (c->dia && c->dia_sym)  // the same blocks from the upper diagonals and their mirrors (cgx_dia_sym.hip)
+            HIPT(dia_sym_diag_blocks_f64(c->n, bs, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
+                                         f64(s.dia_data), c->dia_ld, f64(dD), s.stream));
+        else if (c->dia)  // the same blocks from the diagonals (cgx_dia.hip)
             HIPT(dia_diag_blocks_f64(c->n, bs, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
                                      f64(s.dia_data), c->dia_ld, f64(dD), s.stream));
         else if (c->bsr_bs)  // the same blocks from the BSR arrays, for any bs (cgx_bsmv.hip)
@@ -750,6 +766,21 @@ int cgx_dia_check(int64_t n, int64_t ndiag, const int32_t *offsets) {
         if ((int64_t)offsets[k] <= -n || (int64_t)offsets[k] >= n)
             return fail(CGX_ERR_SHAPE, "cgx_dia_check: offsets[%lld] = %d outside (-%lld, %lld)", (long long)k,
                         (int)offsets[k], (long long)n, (long long)n);
+    return CGX_OK;
+}
+
+int cgx_dia_sym_check(int64_t n, int64_t ndiag, const int32_t *offsets) {
+    if (n < 1 || ndiag < 0) return fail(CGX_ERR_ARG, "cgx_dia_sym_check: n must be >= 1 and ndiag >= 0");
+    if (ndiag > 0 && !offsets) return fail(CGX_ERR_ARG, "cgx_dia_sym_check: NULL pointer");
+    for (int64_t k = 0; k < ndiag; ++k) {
+        if (offsets[k] < 0)
+            return fail(CGX_ERR_SHAPE, "cgx_dia_sym_check: offsets[%lld] = %d is negative: one-sided storage holds "
+                                       "offsets >= 0 (the diagonal -o is the stored diagonal o)", (long long)k,
+                        (int)offsets[k]);
+        if ((int64_t)offsets[k] >= n)
+            return fail(CGX_ERR_SHAPE, "cgx_dia_sym_check: offsets[%lld] = %d outside [0, %lld)", (long long)k,
+                        (int)offsets[k], (long long)n);
+    }
     return CGX_OK;
 }
 
@@ -866,7 +897,29 @@ int cgx_set_dia(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double 
                                    "%lld", (long long)ndiag, (long long)c->n, (double)ndiag * (double)c->n,
                     (long long)c->csr_cap);
     TRY(cgx_dia_check(c->n, ndiag, offsets));  // nothing is uploaded when it fails
-    return dia_upload(c, ndiag, offsets, data, ld);
+    return dia_upload(c, ndiag, offsets, data, ld, /*sym=*/false);
+}
+
+int cgx_set_dia_sym(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld) {
+    const Range range_("cgx_set_dia_sym");
+    if (!c) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: ctx is NULL");
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: not a cgx_create_csr context");
+    if (c->nr)
+        return fail(CGX_ERR_ARG, "cgx_set_dia_sym: not with several right-hand sides (a cgx_create_csr_nrhs context): "
+                                 "batched DIA is not built");
+    if (c->csr_multi)
+        return fail(CGX_ERR_ARG, "cgx_set_dia_sym: not over row blocks (a cgx_create_csr_multi context): DIA over row "
+                                 "blocks is not built");
+    if (ndiag < 0) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: ndiag must be >= 0 (got %lld)", (long long)ndiag);
+    if (ndiag > 0 && (!offsets || !data)) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: offsets / data is NULL");
+    if (ld < c->n)
+        return fail(CGX_ERR_SHAPE, "cgx_set_dia_sym: ld = %lld is below n = %lld", (long long)ld, (long long)c->n);
+    if (ndiag > c->csr_cap / c->n)  // the stored count, not the expansion's; without the product's overflow
+        return fail(CGX_ERR_SHAPE, "cgx_set_dia_sym: %lld stored diagonals of %lld rows are %.0f entries, the context has "
+                                   "room for %lld", (long long)ndiag, (long long)c->n, (double)ndiag * (double)c->n,
+                    (long long)c->csr_cap);
+    TRY(cgx_dia_sym_check(c->n, ndiag, offsets));  // nothing is uploaded when it fails
+    return dia_upload(c, ndiag, offsets, data, ld, /*sym=*/true);
 }
 
 int cgx_spmv_dia(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld, const void *v,
@@ -883,6 +936,23 @@ int cgx_spmv_dia(int64_t n, int64_t ndiag, const void *offsets, const void *data
     HIPT(spmv_dia_f64(pl, static_cast<const int32_t *>(offsets), static_cast<const double *>(data), ld, n, ndiag,
                       static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
                       static_cast<hipStream_t>(stream)));
+    return CGX_OK;
+}
+
+int cgx_spmv_dia_sym(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld, const void *v,
+                     void *out, void *stream) {
+    if (n < 0 || ndiag < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia_sym: bad shape");
+    if (ld < n) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia_sym: ld = %lld is below n = %lld", (long long)ld, (long long)n);
+    if ((ndiag > 0 && (!offsets || !data)) || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_dia_sym: NULL pointer");
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    RedWs ws;
+    TRY(dev_ws(&ws));
+    HIPT(preload_kernels(PL_DIA_SYM));
+    const MatvecPlan pl = plan_spmv_dia_sym(dev, n, ndiag);  // the default rule unless CGX_DIA_SYM_PLAN names a plan
+    HIPT(spmv_dia_sym_f64(pl, static_cast<const int32_t *>(offsets), static_cast<const double *>(data), ld, n, ndiag,
+                          static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
+                          static_cast<hipStream_t>(stream)));
     return CGX_OK;
 }
 

@@ -320,7 +320,8 @@ struct cgx_ctx {
     int64_t bsr_nnzb = 0;
     // cgx_set_dia: the context is diagonal-valued (until the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr), its
     // diagonals and their device pitch (n rounded up to even); csr_nnz is then dia_ndiag * n
-    bool dia = false;
+    // cgx_set_dia_sym: dia with dia_sym, the stored diagonals those of the upper triangle (one-sided)
+    bool dia = false, dia_sym = false;
     int64_t dia_ndiag = 0, dia_ld = 0;
     // cgx_create_csr_multi (whatever the block count): csr_cap is every block's room; halo_counts[d * S + q] =
     // the length of block d's list into block q (cgx_get_csr_halo); csr_halo: several blocks exchange p and x

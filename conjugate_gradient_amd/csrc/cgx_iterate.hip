@@ -108,7 +108,11 @@ int matvec_sym_streamed(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, in
 int launch_matvec(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, int dot_slot, bool gated) {
     TRY(timing_begin(c, s));
     const bool streamed = (c->flags & CGX_HOST_STREAM) != 0;
-    if (c->op == OP_CSR && c->dia)  // diagonal-valued (cgx_set_dia): the same place in the iteration, the diagonal kernel
+    if (c->op == OP_CSR && c->dia && c->dia_sym)  // one-sided (cgx_set_dia_sym): the same place, the one-sided kernel
+        HIPT(spmv_dia_sym_f64(s.plan, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data), c->dia_ld, s.nloc,
+                              c->dia_ndiag, f64(vec), f64(s.Ap), with_dot ? f64(s.pown) : nullptr,
+                              with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream, gate_of(s, gated)));
+    else if (c->op == OP_CSR && c->dia)  // diagonal-valued (cgx_set_dia): the same place in the iteration, the diagonal kernel
         HIPT(spmv_dia_f64(s.plan, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data), c->dia_ld, s.nloc,
                           c->dia_ndiag, f64(vec), f64(s.Ap), with_dot ? f64(s.pown) : nullptr,
                           with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream, gate_of(s, gated)));

@@ -87,7 +87,8 @@ struct MatvecPlan {
     int nrhs = 0;     // > 0: k_matvec_nrhs_f64's plan for this many vectors per pass (2, 4 or 8; nt is 2 or 8)
     int csr = 0;      // 1: k_csr_mult_f64's plan (R = 64 / T rows per wave, U = 1, nt is 2 or 8)
     int bsr = 0;      // > 0 (with csr = 1): k_bsr_mult_f64's plan for this block size (R = 64 / T block rows per wave)
-    int dia = 0;      // 1 (with csr = 1): k_dia_mult_f64's plan (R = 64 or 128 rows per wave, U diagonals in flight)
+    int dia = 0;      // 1 (with csr = 1): k_dia_mult_f64's plan (R = 64 or 128 rows per wave, U diagonals in flight);
+                      // 2: k_dia_sym_mult_f64's, the same ranges (U counts stored diagonals)
 };
 // R/U/nt/blocks_per_cu <= 0 pick the defaults (env CGX_MV_PLAN="R=..,U=..,nt=..,bpc=.."
 // may override).
@@ -292,6 +293,29 @@ hipError_t dia_diag_minv_f64(int64_t n, int64_t ndiag, const int32_t *offsets, c
                              double *minv, unsigned long long *bad, hipStream_t s);
 hipError_t dia_diag_blocks_f64(int64_t n, int pbs, int64_t ndiag, const int32_t *offsets, const double *data,
                                int64_t ld, double *D, hipStream_t s);
+
+// ---- symmetric A held by its upper diagonals (cgx_dia_sym.hip) ----------------------
+// offsets >= 0, data[k * ld + j] = A[j - o][j] for j in [o, n), the stored diagonal of
+// offset o > 0 also standing for the diagonal -o.  out[i] = from +0.0, for k in stored
+// order, fma(data[k][i + o], v[i + o], .) where o > 0 and i + o < n, then
+// fma(data[k][i], v[i - o], .) where i - o >= 0: bit for bit spmv_dia_f64 on the
+// expansion (o, then -o), the fused pown . out included at the same rows per wave and
+// grid.  Slots outside [o, n) are never read; an offset outside [0, n) adds no term
+// and reads nothing outside the arrays.  The 16-byte loads of R = 2 as spmv_dia_f64's.
+// The instantiated (R, U, policy) are spmv_dia_f64's: R in {1, 2}, U in {1, 2, 4, 8}
+// stored diagonals in flight, policy 2 or 8 (of the values' last use: the lower piece
+// and the offset-0 diagonals; the first use is a default-policy load).
+bool spmv_dia_sym_plan_ok(int R, int U, int nt);
+// As plan_spmv_dia, under CGX_DIA_SYM_PLAN="R=..,U=..,nt=..,bpc=..".  pl.csr = 1, pl.dia = 2.
+MatvecPlan plan_spmv_dia_sym(int device, int64_t n, int64_t ndiag, int R = 0, int U = 0, int nt = -1,
+                             int blocks_per_cu = 0);
+hipError_t spmv_dia_sym_f64(const MatvecPlan &pl, const int32_t *offsets, const double *data, int64_t ld, int64_t n,
+                            int64_t ndiag, const double *v, double *out, const double *pown, double *dot_out,
+                            const RedWs &ws, hipStream_t s, const int64_t *gate = nullptr, int64_t *ts = nullptr);
+// The block preconditioner's one-time extraction, bit for bit what csr_diag_blocks_f64
+// gives on the expansion (1 / diag(A) is dia_diag_minv_f64's: only offset 0 counts).
+hipError_t dia_sym_diag_blocks_f64(int64_t n, int pbs, int64_t ndiag, const int32_t *offsets, const double *data,
+                                   int64_t ld, double *D, hipStream_t s);
 
 // ---- several right-hand sides on a CSR matrix (cgx_spmm.hip) ----------------------
 // Out[j*ldo + i] = sum over row i's entries of values[e] * V[j*ldv + col_idx[e]]
@@ -549,10 +573,11 @@ hipError_t preload_pcg();
 hipError_t preload_pcg_block();
 hipError_t preload_bsmv();
 hipError_t preload_dia();
+hipError_t preload_dia_sym();
 enum PreloadSet : unsigned {
     PL_MATVEC = 1, PL_VECTOR = 2, PL_POISSON = 4, PL_REF_F32 = 8, PL_SYMV = 16, PL_MATVEC_A32 = 32,
     PL_MATVEC_NRHS = 64, PL_SPMV = 128, PL_PCG = 256, PL_SPMM = 512, PL_PCG_BLOCK = 1024, PL_BSMV = 2048,
-    PL_DIA = 4096
+    PL_DIA = 4096, PL_DIA_SYM = 8192
 };
 inline hipError_t preload_kernels(unsigned set) {
     const struct { unsigned bit; hipError_t (*fn)(); } all[] = {
@@ -560,7 +585,7 @@ inline hipError_t preload_kernels(unsigned set) {
         {PL_REF_F32, preload_ref_f32}, {PL_SYMV, preload_symv}, {PL_MATVEC_A32, preload_matvec_a32},
         {PL_MATVEC_NRHS, preload_matvec_nrhs}, {PL_SPMV, preload_spmv}, {PL_PCG, preload_pcg},
         {PL_SPMM, preload_spmm}, {PL_PCG_BLOCK, preload_pcg_block}, {PL_BSMV, preload_bsmv},
-        {PL_DIA, preload_dia}};
+        {PL_DIA, preload_dia}, {PL_DIA_SYM, preload_dia_sym}};
     for (const auto &e : all)
         if (set & e.bit) {
             const hipError_t r = e.fn();

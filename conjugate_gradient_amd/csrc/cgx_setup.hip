@@ -868,7 +868,8 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
         info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0) |
                        (c->csr_f32 ? CGX_A_F32 : 0) |  // float-valued since cgx_set_csr_f32
                        (c->bsr_bs ? CGX_BSR_ACTIVE : 0) |  // block-valued since cgx_set_bsr
-                       (c->dia ? CGX_DIA_ACTIVE : 0) |  // diagonal-valued since cgx_set_dia
+                       (c->dia ? CGX_DIA_ACTIVE : 0) |  // diagonal-valued since cgx_set_dia / cgx_set_dia_sym
+                       (c->dia && c->dia_sym ? CGX_DIA_SYM_ACTIVE : 0) |  // ... by the upper diagonals alone
                        (c->csr_halo ? CGX_CSR_HALO_ACTIVE : 0);
     info->elem_bytes = c->es;
     return CGX_OK;

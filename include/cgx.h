@@ -449,7 +449,67 @@
  *       i's entries listed diagonal after diagonal in stored order, in-range
  *       terms only, stored zeros included); the failures are CSR's.
  *     - Not built: float-stored diagonals, several right-hand sides, several
- *       row blocks, one-sided storage of a symmetric A, rectangular matrices.
+ *       row blocks, rectangular matrices.  One-sided storage of a symmetric A
+ *       is the next paragraph.
+ *   - One-sided diagonal storage (cgx_set_dia_sym, on a plain cgx_create_csr
+ *     context): CG needs a symmetric A, so the diagonals of triu(A) say
+ *     everything.  Each stored value is used twice, o rows apart: the byte
+ *     model is 8 ndiag_stored + 16 per row (5-point Poisson: 40 in place of
+ *     56; 65 diagonals: 280 in place of 536) where the second use finds its
+ *     line on the die, and the matrix needs half the memory.  Symmetry
+ *     cannot be checked -- only one triangle is given: what is multiplied is
+ *     the symmetric matrix whose upper triangle the arrays hold.
+ *     - Storage (scipy's dia_matrix of triu(A)): offsets is int32_t[ndiag]
+ *       with 0 <= offsets[k] < n, data double[ndiag * ld] with ld >= n;
+ *       data[k * ld + j] = A[j - o][j] for j in [o, n), o = offsets[k].  Slots
+ *       j < o and j >= n are never read, on the host or on the device, and
+ *       may hold NaN.  The stored diagonal of offset o > 0 also stands for
+ *       the diagonal -o: A[j][j - o] = A[j - o][j].  Diagonals are taken in
+ *       stored order and need not be sorted, a duplicate offset is two terms,
+ *       each with its mirror, a stored zero is a term.  ndiag = 0 is the zero
+ *       matrix.
+ *     - Summation order (k_dia_sym_mult_f64).  Row i starts from +0.0 and,
+ *       for k = 0 .. ndiag-1 in stored order: o = 0 does
+ *       acc = fma(data[k][i], v[i], acc); o > 0 does the upper term first,
+ *       acc = fma(data[k][i + o], v[i + o], acc) where i + o < n, then the
+ *       lower term acc = fma(data[k][i], v[i - o], acc) where i - o >= 0.
+ *       One accumulator per row, no cross-lane combine; a row's sum depends
+ *       on nothing but the matrix and v.  The expansion: this is, bit for
+ *       bit, what k_dia_mult_f64 gives on the full DIA matrix in which every
+ *       stored k with o > 0 is two consecutive diagonals, o then -o (the
+ *       mirrored one data'[j] = data[k][j + o], j in [0, n - o)) and a
+ *       diagonal with o = 0 stays one.  The fused p.Ap is that kernel's on
+ *       the expansion at the same rows per lane and grid.
+ *     - cgx_dia_sym_check (host only): n < 1, ndiag < 0 or NULL offsets with
+ *       ndiag > 0 is CGX_ERR_ARG; an offset < 0 or >= n is CGX_ERR_SHAPE, the
+ *       first such k and its value named (a negative one with the reminder
+ *       that one-sided storage holds offsets >= 0).
+ *     - cgx_set_dia_sym runs cgx_set_dia's checks in cgx_set_dia's order; the
+ *       capacity check compares ndiag n, the stored count (not the
+ *       expansion's), with the creation-time nnz; cgx_dia_sym_check is last.
+ *       Nothing is uploaded when one fails: the earlier matrix (CSR, BSR, DIA
+ *       or one-sided), its value type, plan and preconditioner stay.
+ *     - A successful call ends a solve in progress, turns preconditioning
+ *       off, makes a new default plan unless the caller chose one on a
+ *       one-sided context already, and makes the context one-sided until the
+ *       next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr / cgx_set_dia, after
+ *       which the context gives a fresh context's bits.  cgx_get_info: flags
+ *       carries CGX_DIA_SYM_ACTIVE | CGX_DIA_ACTIVE | CGX_CSR_ACTIVE.
+ *     - cgx_set_matvec_plan: as on a diagonal-valued context (rows_per_wave
+ *       64 or 128, chunks_in_flight 1, 2, 4 or 8 stored diagonals, policy 2
+ *       or 8 -- of the values' last use; the first use is a default-policy
+ *       load).  CGX_DIA_SYM_PLAN="R=..,U=..,nt=..,bpc=.." (R = 1 or 2)
+ *       overrides the default.
+ *     - The iteration is untouched; only the matVec (and cgx_residual_norm's)
+ *       is the one-sided kernel.
+ *     - Preconditioners: cgx_set_precond_diag and
+ *       cgx_set_precond_block_values never read the matrix.  CGX_PC_JACOBI
+ *       (the offset-0 diagonals) and cgx_set_precond_block(pbs), pbs in 2..8
+ *       (row r takes, per stored k with o > 0, (r + o, data[k][r + o]) then
+ *       (r - o, data[k][r])) give, bit for bit, what a double-valued CSR
+ *       context gives on the expansion; the failures are CSR's.
+ *     - Not built: float-stored one-sided values, several right-hand sides,
+ *       row blocks, one-sided BSR.
  *
  * Multi-GPU: the matrix is split into contiguous row blocks (parallel_cg.c:83,
  * 97-99; n % nranks == 0 as parallel_cg.c:86-90 requires).  Per iteration
@@ -484,7 +544,9 @@ extern "C" {
                            cgx_get_csr_halo and cgx_gather_indexed, and the reported bit
                            CGX_CSR_HALO_ACTIVE; likewise cgx_set_bsr, cgx_bsr_check, cgx_spmv_bsr and
                            cgx_bsr_tile_values, and the reported bit CGX_BSR_ACTIVE; likewise cgx_set_dia,
-                           cgx_dia_check and cgx_spmv_dia, and the reported bit CGX_DIA_ACTIVE */
+                           cgx_dia_check and cgx_spmv_dia, and the reported bit CGX_DIA_ACTIVE; likewise
+                           cgx_set_dia_sym, cgx_dia_sym_check and cgx_spmv_dia_sym, and the reported bit
+                           CGX_DIA_SYM_ACTIVE */
 
 /* ---- status codes (0 = OK, negative = error) --------------------------- */
 #define CGX_OK            0
@@ -502,6 +564,9 @@ extern "C" {
 #define CGX_A_F32        0x2   /* float A, double vectors and arithmetic (above) */
 #define CGX_DIA_ACTIVE   0x4   /* reported in cgx_info.flags: a cgx_create_csr context that is
                                   diagonal-valued (cgx_set_dia), beside CGX_CSR_ACTIVE */
+#define CGX_DIA_SYM_ACTIVE 0x8 /* reported in cgx_info.flags: a diagonal-valued context that holds the
+                                  upper diagonals of a symmetric A (cgx_set_dia_sym), beside
+                                  CGX_DIA_ACTIVE | CGX_CSR_ACTIVE */
 #define CGX_TIMING       0x100 /* time every matVec launch with HIP events      */
 #define CGX_NO_OVERLAP   0x400 /* multi-shard dense fp64: do not overlap the p
                                   exchange with the own-column-block matVec
@@ -840,6 +905,15 @@ int cgx_dia_check(int64_t n, int64_t ndiag, const int32_t *offsets);
  * ndiag * n at most the context's nnz); makes a plain cgx_create_csr context diagonal-valued until
  * the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr.  Checks and effects: "Diagonal storage" above. */
 int cgx_set_dia(cgx_ctx *ctx, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld);
+/* ---- one-sided diagonal storage of a symmetric A (see "One-sided diagonal storage" above) ---- */
+/* Host-only: n >= 1, ndiag >= 0, every offset inside [0, n) -- CGX_ERR_SHAPE names the first
+ * offsets[k] outside and its value. */
+int cgx_dia_sym_check(int64_t n, int64_t ndiag, const int32_t *offsets);
+/* Host arrays in scipy's dia_matrix layout of triu(A) (data[k * ld + j] = A[j - offsets[k]][j] for j in
+ * [offsets[k], n), ld >= n, ndiag * n at most the context's nnz); makes a plain cgx_create_csr context
+ * one-sided until the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr / cgx_set_dia.  Symmetry cannot be
+ * checked: only one triangle is given. */
+int cgx_set_dia_sym(cgx_ctx *ctx, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld);
 /* One GPU, fp64: nrhs (1..CGX_MAX_NRHS) systems A x_j = b_j on one CSR matrix with room for
  * nnz entries, solved together, one read of the CSR arrays per iteration.
  * flags: CGX_F64, optionally CGX_TIMING.  Arguments are checked before any device is touched. */
@@ -1034,6 +1108,13 @@ int cgx_spmv_bsr(int64_t nb, int64_t ncolb, int bs, const void *brow_ptr, const 
  * CGX_DIA_PLAN="R=..,U=..,nt=..,bpc=.." (default: the context's rule). */
 int cgx_spmv_dia(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld,
                  const void *v, void *out, void *stream);
+/* Kernel-level, device pointers: out = A v, A the symmetric matrix whose upper diagonals offsets / data
+ * hold, in the order of "One-sided diagonal storage" above -- bit for bit cgx_spmv_dia on the expansion;
+ * offsets is int32[ndiag], data double[ndiag * ld], ld >= n.  The offsets should have passed
+ * cgx_dia_sym_check; one outside [0, n) adds no term.  The plan comes from
+ * CGX_DIA_SYM_PLAN="R=..,U=..,nt=..,bpc=.." (default: the context's rule). */
+int cgx_spmv_dia_sym(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld,
+                     const void *v, void *out, void *stream);
 /* Kernel-level, device pointers: Out[j*ldo + i] = sum_e values[e] * V[j*ldv + col_idx[e]],
  * j < nrhs.  Column j is cgx_spmv_csr's result on column j bit for bit at the same T.
  * The indices must have passed cgx_csr_check.  T comes from
