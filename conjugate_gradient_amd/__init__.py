@@ -584,14 +584,42 @@ def _dia_arrays(what: str, offsets, data=None):
     return np.ascontiguousarray(o, np.int32), np.ascontiguousarray(d, np.float64)
 
 
+def _dia_check(what: str, offsets, n) -> None:
+    """dia_check / dia_sym_check under the caller's name ``what`` (cgx_<what> is the C call)."""
+    o = np.asarray(offsets)
+    _need(o.ndim == 1 and (o.dtype.kind in "iu" or o.size == 0), f"{what}: offsets are one-dimensional integers")
+    _need(isinstance(n, (int, np.integer)), f"{what}: n is an integer")
+    _need(o.size == 0 or (int(o.min()) >= -2**31 and int(o.max()) < 2**31), f"{what}: an offset does not fit int32")
+    o = np.ascontiguousarray(o, np.int32)
+    _check(getattr(lib(), f"cgx_{what}")(int(n), o.size, _ptr(o) if o.size else None), f"cgx_{what}")
+
+
+def _spmv_dia(what: str, sym: bool, offsets, data, v: DeviceArray, out: DeviceArray, n) -> None:
+    """spmv_dia / spmv_dia_sym under the caller's name ``what`` (cgx_<what> is the C call)."""
+    o, d = _dia_arrays(what, offsets, data)
+    _need(isinstance(n, (int, np.integer)) and n >= 1, f"{what}: need an integer n >= 1")
+    ld = int(d.shape[1])
+    _need(ld >= n, f"{what}: data has {ld} columns, n = {n} needed")
+    _need(v.dtype == np.float64 and out.dtype == np.float64, f"{what}: float64 only")
+    _fits([v], n, f"{what} v")
+    _fits([out], n, f"{what} out")
+    L = lib()
+    check = "cgx_dia_sym_check" if sym else "cgx_dia_check"
+    _check(getattr(L, check)(int(n), o.size, _ptr(o) if o.size else None), check)
+    ndiag = int(o.size)
+    d_o = DeviceArray.from_host(o if ndiag else np.zeros(1, np.int32))
+    d_d = DeviceArray.from_host(d.reshape(-1) if ndiag else np.zeros(1))
+    try:
+        _check(getattr(L, f"cgx_{what}")(int(n), ndiag, d_o.ptr, d_d.ptr, ld, v.ptr, out.ptr, None), f"cgx_{what}")
+        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
+    finally:
+        for a in (d_o, d_d):
+            a.free()
+
+
 def dia_check(offsets, n: int) -> None:
     """cgx_dia_check (host only, no GPU): raises CgxError(-4) naming the first offset outside (-n, n)."""
-    o = np.asarray(offsets)
-    _need(o.ndim == 1 and (o.dtype.kind in "iu" or o.size == 0), "dia_check: offsets are one-dimensional integers")
-    _need(isinstance(n, (int, np.integer)), "dia_check: n is an integer")
-    _need(o.size == 0 or (int(o.min()) >= -2**31 and int(o.max()) < 2**31), "dia_check: an offset does not fit int32")
-    o = np.ascontiguousarray(o, np.int32)
-    _check(lib().cgx_dia_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_check")
+    _dia_check("dia_check", offsets, n)
 
 
 def spmv_dia(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> None:
@@ -599,36 +627,13 @@ def spmv_dia(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> None:
     data[k, i + offsets[k]] * v[i + offsets[k]], i < n (k_dia_mult_f64; the plan from CGX_DIA_PLAN).  ``data`` has
     shape (ndiag, ld), ld >= n, scipy's dia_matrix layout.  The offsets come as a host array: they are checked
     (cgx_dia_check) and only then uploaded; slots of ``data`` that hold no entry of A are never read by the kernel."""
-    o, d = _dia_arrays("spmv_dia", offsets, data)
-    _need(isinstance(n, (int, np.integer)) and n >= 1, "spmv_dia: need an integer n >= 1")
-    ld = int(d.shape[1])
-    _need(ld >= n, f"spmv_dia: data has {ld} columns, n = {n} needed")
-    _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_dia: float64 only")
-    _fits([v], n, "spmv_dia v")
-    _fits([out], n, "spmv_dia out")
-    L = lib()
-    _check(L.cgx_dia_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_check")
-    ndiag = int(o.size)
-    d_o = DeviceArray.from_host(o if ndiag else np.zeros(1, np.int32))
-    d_d = DeviceArray.from_host(d.reshape(-1) if ndiag else np.zeros(1))
-    try:
-        _check(L.cgx_spmv_dia(int(n), ndiag, d_o.ptr, d_d.ptr, ld, v.ptr, out.ptr, None), "cgx_spmv_dia")
-        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
-    finally:
-        for a in (d_o, d_d):
-            a.free()
+    _spmv_dia("spmv_dia", False, offsets, data, v, out, n)
 
 
 def dia_sym_check(offsets, n: int) -> None:
     """cgx_dia_sym_check (host only, no GPU): raises CgxError(-4) naming the first offset outside [0, n) -- one-sided
     storage holds offsets >= 0, the diagonal -o is the stored diagonal o."""
-    o = np.asarray(offsets)
-    _need(o.ndim == 1 and (o.dtype.kind in "iu" or o.size == 0), "dia_sym_check: offsets are one-dimensional integers")
-    _need(isinstance(n, (int, np.integer)), "dia_sym_check: n is an integer")
-    _need(o.size == 0 or (int(o.min()) >= -2**31 and int(o.max()) < 2**31),
-          "dia_sym_check: an offset does not fit int32")
-    o = np.ascontiguousarray(o, np.int32)
-    _check(lib().cgx_dia_sym_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_sym_check")
+    _dia_check("dia_sym_check", offsets, n)
 
 
 def spmv_dia_sym(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> None:
@@ -638,24 +643,41 @@ def spmv_dia_sym(offsets, data, v: DeviceArray, out: DeviceArray, n: int) -> Non
     -- the bits of :func:`spmv_dia` on the expansion (o, then -o).  ``data`` has shape (ndiag, ld), ld >= n.  The
     offsets come as a host array: they are checked (cgx_dia_sym_check) and only then uploaded; slots outside
     [o, n) are never read by the kernel."""
-    o, d = _dia_arrays("spmv_dia_sym", offsets, data)
-    _need(isinstance(n, (int, np.integer)) and n >= 1, "spmv_dia_sym: need an integer n >= 1")
-    ld = int(d.shape[1])
-    _need(ld >= n, f"spmv_dia_sym: data has {ld} columns, n = {n} needed")
-    _need(v.dtype == np.float64 and out.dtype == np.float64, "spmv_dia_sym: float64 only")
-    _fits([v], n, "spmv_dia_sym v")
-    _fits([out], n, "spmv_dia_sym out")
-    L = lib()
-    _check(L.cgx_dia_sym_check(int(n), o.size, _ptr(o) if o.size else None), "cgx_dia_sym_check")
-    ndiag = int(o.size)
-    d_o = DeviceArray.from_host(o if ndiag else np.zeros(1, np.int32))
-    d_d = DeviceArray.from_host(d.reshape(-1) if ndiag else np.zeros(1))
+    _spmv_dia("spmv_dia_sym", True, offsets, data, v, out, n)
+
+
+def _from_dia(cls, what: str, setter: str, offsets, data, n, precond, device, flags) -> "Solver":
+    """Solver.from_dia / from_dia_sym under the caller's name ``what``; ``setter`` is the kind's set_dia / set_dia_sym."""
+    if n is None and data is None and hasattr(offsets, "shape") and hasattr(offsets, "offsets"):
+        n = int(offsets.shape[0])
+    o, d = _dia_arrays(what, offsets, data)
+    n = int(d.shape[1]) if n is None else n
+    _need(isinstance(n, (int, np.integer)) and n >= 1, f"{what}: n must be an integer >= 1 (got {n})")
+    _need(d.shape[1] >= n, f"{what}: data has {d.shape[1]} columns, n = {n} needed")
+    s = cls.csr(int(n), int(o.size) * int(n), device=device, flags=flags)
     try:
-        _check(L.cgx_spmv_dia_sym(int(n), ndiag, d_o.ptr, d_d.ptr, ld, v.ptr, out.ptr, None), "cgx_spmv_dia_sym")
-        _check(L.cgx_dev_synchronize(), "cgx_dev_synchronize")
-    finally:
-        for a in (d_o, d_d):
-            a.free()
+        getattr(s, setter)(o, d)
+        if precond is not None:
+            s.set_precond(precond)
+    except Exception:
+        s.close()
+        raise
+    return s
+
+
+def _set_dia(self, what: str, noun: str, offsets, data) -> None:
+    """Solver.set_dia / set_dia_sym under the caller's name ``what`` (cgx_<what> is the C call); ``noun`` is what the
+    room is counted in."""
+    _need(getattr(self, "csr_nnz", None) is not None, f"{what}: the solver was not created with csr_nnz=")
+    _need(getattr(self, "devices", None) is None and getattr(self, "nrhs", None) is None,
+          f"{what}: diagonal storage runs on one GPU with one right-hand side (not with devices= or nrhs=)")
+    o, d = _dia_arrays(what, offsets, data)
+    _need(d.shape[1] >= self.n, f"{what}: data has {d.shape[1]} columns, n = {self.n} needed")
+    _need(o.size * self.n <= self.csr_nnz,
+          f"{what}: {o.size} {noun} of {self.n} rows are {o.size * self.n} entries, the solver has room for "
+          f"{self.csr_nnz}")
+    _check(getattr(lib(), f"cgx_{what}")(self._h, int(o.size), _ptr(o) if o.size else None,
+                                         _ptr(d) if o.size else None, int(d.shape[1])), f"cgx_{what}")
 
 
 def bsr_check(indptr, indices, nb: int | None = None) -> None:
@@ -1053,21 +1075,7 @@ class Solver:
         through :meth:`set_dia` (b = 0, x0 = 0) and, with ``precond`` ("jacobi", an array or ``("block", pbs)``),
         its preconditioner (:meth:`set_precond`).  ``data`` has shape (ndiag, ld); or pass one object with
         ``.offsets / .data`` such as scipy's dia_matrix.  ``n`` defaults to the object's ``shape[0]``, else to ld."""
-        if n is None and data is None and hasattr(offsets, "shape") and hasattr(offsets, "offsets"):
-            n = int(offsets.shape[0])
-        o, d = _dia_arrays("from_dia", offsets, data)
-        n = int(d.shape[1]) if n is None else n
-        _need(isinstance(n, (int, np.integer)) and n >= 1, f"from_dia: n must be an integer >= 1 (got {n})")
-        _need(d.shape[1] >= n, f"from_dia: data has {d.shape[1]} columns, n = {n} needed")
-        s = cls.csr(int(n), int(o.size) * int(n), device=device, flags=flags)
-        try:
-            s.set_dia(o, d)
-            if precond is not None:
-                s.set_precond(precond)
-        except Exception:
-            s.close()
-            raise
-        return s
+        return _from_dia(cls, "from_dia", "set_dia", offsets, data, n, precond, device, flags)
 
     def set_dia(self, offsets, data=None) -> None:
         """cgx_set_dia: the matrix of a ``csr_nnz`` solver held by diagonals, scipy's dia_matrix layout (``data`` of
@@ -1077,16 +1085,7 @@ class Solver:
         earlier matrix stays.  The solver is diagonal-valued (``info().flags`` carries CGX_DIA_ACTIVE) until the
         next :meth:`set_csr` / :meth:`set_bsr`; preconditioning is off afterwards, as after ``set_csr``.  One GPU,
         one right-hand side, float64 values."""
-        _need(getattr(self, "csr_nnz", None) is not None, "set_dia: the solver was not created with csr_nnz=")
-        _need(getattr(self, "devices", None) is None and getattr(self, "nrhs", None) is None,
-              "set_dia: diagonal storage runs on one GPU with one right-hand side (not with devices= or nrhs=)")
-        o, d = _dia_arrays("set_dia", offsets, data)
-        _need(d.shape[1] >= self.n, f"set_dia: data has {d.shape[1]} columns, n = {self.n} needed")
-        _need(o.size * self.n <= self.csr_nnz,
-              f"set_dia: {o.size} diagonals of {self.n} rows are {o.size * self.n} entries, the solver has room for "
-              f"{self.csr_nnz}")
-        _check(lib().cgx_set_dia(self._h, int(o.size), _ptr(o) if o.size else None, _ptr(d) if o.size else None,
-                                 int(d.shape[1])), "cgx_set_dia")
+        _set_dia(self, "set_dia", "diagonals", offsets, data)
 
     @classmethod
     def from_dia_sym(cls, offsets, data=None, *, n: int | None = None, precond=None, device: int = 0,
@@ -1094,21 +1093,7 @@ class Solver:
         """A CSR solver sized for this symmetric matrix held by its upper diagonals (room for ndiag * n entries, the
         stored count), with the matrix set through :meth:`set_dia_sym` (b = 0, x0 = 0) and, with ``precond``, its
         preconditioner (:meth:`set_precond`).  Arguments as :meth:`from_dia`'s."""
-        if n is None and data is None and hasattr(offsets, "shape") and hasattr(offsets, "offsets"):
-            n = int(offsets.shape[0])
-        o, d = _dia_arrays("from_dia_sym", offsets, data)
-        n = int(d.shape[1]) if n is None else n
-        _need(isinstance(n, (int, np.integer)) and n >= 1, f"from_dia_sym: n must be an integer >= 1 (got {n})")
-        _need(d.shape[1] >= n, f"from_dia_sym: data has {d.shape[1]} columns, n = {n} needed")
-        s = cls.csr(int(n), int(o.size) * int(n), device=device, flags=flags)
-        try:
-            s.set_dia_sym(o, d)
-            if precond is not None:
-                s.set_precond(precond)
-        except Exception:
-            s.close()
-            raise
-        return s
+        return _from_dia(cls, "from_dia_sym", "set_dia_sym", offsets, data, n, precond, device, flags)
 
     def set_dia_sym(self, offsets, data=None) -> None:
         """cgx_set_dia_sym: the symmetric matrix of a ``csr_nnz`` solver held by the diagonals of its upper triangle,
@@ -1121,16 +1106,7 @@ class Solver:
         (``info().flags`` carries CGX_DIA_SYM_ACTIVE | CGX_DIA_ACTIVE) until the next :meth:`set_csr` /
         :meth:`set_bsr` / :meth:`set_dia`; preconditioning is off afterwards.  One GPU, one right-hand side,
         float64 values."""
-        _need(getattr(self, "csr_nnz", None) is not None, "set_dia_sym: the solver was not created with csr_nnz=")
-        _need(getattr(self, "devices", None) is None and getattr(self, "nrhs", None) is None,
-              "set_dia_sym: diagonal storage runs on one GPU with one right-hand side (not with devices= or nrhs=)")
-        o, d = _dia_arrays("set_dia_sym", offsets, data)
-        _need(d.shape[1] >= self.n, f"set_dia_sym: data has {d.shape[1]} columns, n = {self.n} needed")
-        _need(o.size * self.n <= self.csr_nnz,
-              f"set_dia_sym: {o.size} stored diagonals of {self.n} rows are {o.size * self.n} entries, the solver has "
-              f"room for {self.csr_nnz}")
-        _check(lib().cgx_set_dia_sym(self._h, int(o.size), _ptr(o) if o.size else None,
-                                     _ptr(d) if o.size else None, int(d.shape[1])), "cgx_set_dia_sym")
+        _set_dia(self, "set_dia_sym", "stored diagonals", offsets, data)
 
     def csr_halo(self) -> np.ndarray:
         """cgx_get_csr_halo: the ``(nshards, nshards)`` exchange counts in use on a CSR solver over row blocks

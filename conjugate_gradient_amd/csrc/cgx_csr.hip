@@ -54,32 +54,22 @@ int csr_plan_args(int K, int R, int U, int nt) {
 }
 
 int csr_set_plan(cgx_ctx *c, int R, int U, int nt, int blocks_per_cu) {
-    if (c->dia && c->dia_sym) {  // one-sided: the diagonal kernel's ranges, U stored diagonals in flight
-        if ((R != 64 && R != 128) || !spmv_dia_sym_plan_ok(R / 64, U, nt))
-            return fail(CGX_ERR_ARG, "one-sided diagonal-valued cgx_create_csr context: rows_per_wave must be 64 or "
-                                     "128, chunks_in_flight 1, 2, 4 or 8 and the load policy 2 or 8 (got %d, %d, %d)",
-                        R, U, nt);
-        Shard &s = c->sh[0];
-        TRY(set_dev(s));
-        s.plan = plan_spmv_dia_sym(s.dev, s.nloc, c->dia_ndiag, R / 64, U, nt, blocks_per_cu);
-        c->csr_plan_user = true;
-        return CGX_OK;
-    }
-    if (c->dia) {  // diagonal-valued: 64 or 128 rows per wave, U diagonals in flight
-        if ((R != 64 && R != 128) || !spmv_dia_plan_ok(R / 64, U, nt))
-            return fail(CGX_ERR_ARG, "diagonal-valued cgx_create_csr context: rows_per_wave must be 64 or 128, "
+    if (is_dia(c)) {  // the diagonal kernels' ranges: 64 or 128 rows per wave, U (stored) diagonals in flight
+        const DiaKind &dk = dia_kind(c);
+        if ((R != 64 && R != 128) || !dk.plan_ok(R / 64, U, nt))
+            return fail(CGX_ERR_ARG, "%sdiagonal-valued cgx_create_csr context: rows_per_wave must be 64 or 128, "
                                      "chunks_in_flight 1, 2, 4 or 8 and the load policy 2 or 8 (got %d, %d, %d)",
-                        R, U, nt);
+                        dk.prefix, R, U, nt);
         Shard &s = c->sh[0];
         TRY(set_dev(s));
-        s.plan = plan_spmv_dia(s.dev, s.nloc, c->dia_ndiag, R / 64, U, nt, blocks_per_cu);
+        s.plan = dk.plan(s.dev, s.nloc, c->dia_ndiag, R / 64, U, nt, blocks_per_cu);
         c->csr_plan_user = true;
         return CGX_OK;
     }
     TRY(csr_plan_args(1, R, U, nt));
     for (auto &s : c->sh) {  // one T for every row block, each block's grid from its own rows
         TRY(set_dev(s));
-        if (c->bsr_bs)  // block-valued: T lanes per block row
+        if (c->storage == SK_BSR)  // block-valued: T lanes per block row
             s.plan = plan_spmv_bsr(s.dev, s.nloc / c->bsr_bs, c->bsr_nnzb, c->bsr_bs, 64 / R, nt, blocks_per_cu);
         else
             s.plan = plan_spmv_csr(s.dev, s.nloc, c->csr_nnz >= 0 ? c->csr_nnz : c->csr_cap, 64 / R, nt,
@@ -163,6 +153,54 @@ static int pc_drop(cgx_ctx *c) {
     return CGX_OK;
 }
 
+// The context's storage becomes `to`.  A caller's plan (cgx_set_matvec_plan) goes with the move where its
+// vocabulary does: CSR and BSR plans both count T lanes per (block) row, a diagonal plan counts rows per lane and
+// names its own kind's kernel.
+static void csr_storage_to(cgx_ctx *c, Storage to) {
+    if (to != c->storage && (is_dia(c) || to == SK_DIA || to == SK_DIA_SYM)) c->csr_plan_user = false;
+    c->storage = to;
+}
+
+// An upload failed with part of the new matrix on the device: a scalar context with no matrix until the next
+// successful upload.
+static void csr_no_matrix(cgx_ctx *c) {
+    csr_storage_to(c, SK_CSR);
+    c->csr_nnz = -1;
+    c->state = ST_IDLE;
+}
+
+// The end of every successful upload on one block (csr_upload, bsr_upload, dia_upload; the kind's own parameters
+// are set): the matrix is of storage `to` with nnz entries, the preconditioner of the old matrix goes, and the plan
+// is the caller's T and policy (rows per lane, diagonals in flight and policy) on the new matrix where it carries
+// over, the default rule's otherwise.
+static int csr_set_storage(cgx_ctx *c, Storage to, int64_t nnz, bool f32) {
+    Shard &s = c->sh[0];
+    const Storage was = c->storage;
+    csr_storage_to(c, to);
+    c->csr_nnz = nnz;
+    c->csr_f32 = f32;
+    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
+    const bool user = c->csr_plan_user;
+    switch (to) {
+        case SK_CSR:
+            if (!user && c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs), 0, -1, 0, f32);
+            else if (!user) s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 0, -1, 0, f32);
+            else if (was == SK_BSR) s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 64 / s.plan.R, s.plan.nt, 0, f32);
+            break;  // the tiled buffer of a block-valued context stays
+        case SK_BSR:
+            s.plan = user ? plan_spmv_bsr(s.dev, s.nloc / c->bsr_bs, c->bsr_nnzb, c->bsr_bs, 64 / s.plan.R, s.plan.nt)
+                          : plan_spmv_bsr(s.dev, s.nloc / c->bsr_bs, c->bsr_nnzb, c->bsr_bs);
+            break;
+        case SK_DIA:
+        case SK_DIA_SYM:
+            s.plan = user ? dia_kind(c).plan(s.dev, s.nloc, c->dia_ndiag, s.plan.R / 64, s.plan.U, s.plan.nt, 0)
+                          : dia_kind(c).plan(s.dev, s.nloc, c->dia_ndiag, 0, 0, -1, 0);
+            break;
+    }
+    c->state = ST_IDLE;
+    return CGX_OK;
+}
+
 // What every call that sets a preconditioner checks first: the context's kind ...
 static int pc_need_ctx(const cgx_ctx *c, const char *what) {
     if (!c) return fail(CGX_ERR_ARG, "%s: ctx is NULL", what);
@@ -200,19 +238,24 @@ static int pc_jacobi(cgx_ctx *c) {
         unsigned long long *pin = reinterpret_cast<unsigned long long *>(s.h_pin);
         pin[0] = ~0ull;
         HIPT(hipMemcpyAsync(slot(s, S_PCBAD), pin, 8, hipMemcpyHostToDevice, s.stream));
-        if (c->dia) {
-            HIPT(dia_diag_minv_f64(c->n, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data),
-                                   c->dia_ld, f64(fresh), static_cast<unsigned long long *>(slot(s, S_PCBAD)),
-                                   s.stream));
-        } else if (c->bsr_bs) {
-            HIPT(preload_kernels(PL_BSMV));
-            HIPT(bsr_diag_minv_f64(c->n, c->bsr_bs, reinterpret_cast<const int64_t *>(s.csr_rp),
-                                   reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(fresh),
-                                   static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
-        } else {
-            HIPT(csr_diag_minv_f64(c->n, reinterpret_cast<const int64_t *>(s.csr_rp),
-                                   reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(fresh),
-                                   static_cast<unsigned long long *>(slot(s, S_PCBAD)), s.stream));
+        unsigned long long *bad_row = static_cast<unsigned long long *>(slot(s, S_PCBAD));
+        switch (c->storage) {
+            case SK_DIA:
+            case SK_DIA_SYM:  // only offset 0 counts: one extraction for both kinds
+                HIPT(dia_diag_minv_f64(c->n, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
+                                       f64(s.dia_data), c->dia_ld, f64(fresh), bad_row, s.stream));
+                break;
+            case SK_BSR:
+                HIPT(preload_kernels(PL_BSMV));
+                HIPT(bsr_diag_minv_f64(c->n, c->bsr_bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                       reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(fresh), bad_row,
+                                       s.stream));
+                break;
+            case SK_CSR:
+                HIPT(csr_diag_minv_f64(c->n, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                       reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(fresh), bad_row,
+                                       s.stream));
+                break;
         }
         HIPT(hipMemcpyAsync(pin, slot(s, S_PCBAD), 8, hipMemcpyDeviceToHost, s.stream));
         HIPT(hipStreamSynchronize(s.stream));
@@ -355,8 +398,7 @@ static int csr_upload_blocks(cgx_ctx *c, const int64_t *row_ptr, const int32_t *
     }();
     if (rc != CGX_OK) {  // some blocks hold the new rows, some the old: no matrix until the next cgx_set_csr
         drop_fresh();
-        c->csr_nnz = -1;
-        c->state = ST_IDLE;
+        csr_no_matrix(c);
         return rc;
     }
     for (int i = 0; i < S; ++i) {
@@ -412,22 +454,7 @@ static int csr_upload(cgx_ctx *c, const int64_t *row_ptr, const int32_t *col_idx
         HIPT(hipMemcpyAsync(s.csr_val, values, (size_t)nnz * (f32 ? 4 : 8), hipMemcpyHostToDevice, s.stream));
     }
     HIPT(hipStreamSynchronize(s.stream));
-    c->csr_nnz = nnz;
-    c->csr_f32 = f32;
-    const bool was_bsr = c->bsr_bs != 0;  // block-valued until now: a scalar context again (the tiled buffer stays)
-    c->bsr_bs = 0;
-    c->bsr_nnzb = 0;
-    if (c->dia) c->csr_plan_user = false;  // a diagonal plan counts rows per lane: it says nothing about T
-    c->dia = c->dia_sym = false;
-    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
-    if (!c->csr_plan_user) {
-        if (c->nr) c->nr->plan = plan_spmm_csr(s.dev, s.nloc, nnz, nrhs_width(c->nr->nrhs), 0, -1, 0, f32);
-        else s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 0, -1, 0, f32);
-    } else if (was_bsr) {  // the caller's T and policy, on scalar rows again
-        s.plan = plan_spmv_csr(s.dev, s.nloc, nnz, 64 / s.plan.R, s.plan.nt, 0, f32);
-    }
-    c->state = ST_IDLE;
-    return CGX_OK;
+    return csr_set_storage(c, SK_CSR, nnz, f32);
 }
 
 // What cgx_csr_check and cgx_bsr_check test, under the caller's names.
@@ -484,10 +511,7 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
     }();
     if (rc != CGX_OK) {  // part of the new matrix is on the device: no matrix until the next cgx_set_csr / cgx_set_bsr
         if (fresh) (void)hipFree(fresh);
-        c->csr_nnz = -1;
-        c->bsr_bs = 0;
-        c->dia = c->dia_sym = false;
-        c->state = ST_IDLE;
+        csr_no_matrix(c);
         return rc;
     }
     if (fresh) {
@@ -495,17 +519,9 @@ static int bsr_upload(cgx_ctx *c, int bs, int64_t nnzb, const int64_t *brow_ptr,
         s.bsr_val = fresh;
         s.bsr_cap = need;
     }
-    c->csr_nnz = nnzb * bs * bs;
-    c->csr_f32 = false;
     c->bsr_bs = bs;
     c->bsr_nnzb = nnzb;
-    if (c->dia) c->csr_plan_user = false;  // a diagonal plan counts rows per lane: it says nothing about T
-    c->dia = c->dia_sym = false;
-    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
-    if (!c->csr_plan_user) s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs);
-    else s.plan = plan_spmv_bsr(s.dev, nb, nnzb, bs, 64 / s.plan.R, s.plan.nt);  // the caller's T and policy
-    c->state = ST_IDLE;
-    return CGX_OK;
+    return csr_set_storage(c, SK_BSR, nnzb * bs * bs, /*f32=*/false);
 }
 
 // cgx_set_dia, after its checks: the offsets go into col_idx's place, the
@@ -518,7 +534,7 @@ static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const d
     const int64_t pitch = round_up(c->n, 2), need = ndiag * pitch;  // ndiag n <= csr_cap: no overflow
     TRY(sync_all(c));  // iterations still enqueued read the arrays
     TRY(set_dev(s));
-    HIPT(preload_kernels(sym ? PL_DIA | PL_DIA_SYM : PL_DIA));  // CGX_PC_JACOBI's extraction is the diagonal file's
+    HIPT(preload_kernels(kDiaKinds[sym].preload_ctx));
     char *fresh = nullptr;
     if (need > c->csr_cap && need > s.dia_cap) {
         const hipError_t e = hipMalloc(&fresh, (size_t)need * 8);
@@ -538,10 +554,7 @@ static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const d
     }();
     if (rc != CGX_OK) {  // part of the new matrix is on the device: no matrix until the next cgx_set_csr / cgx_set_dia
         if (fresh) (void)hipFree(fresh);
-        c->csr_nnz = -1;
-        c->bsr_bs = 0;
-        c->dia = c->dia_sym = false;
-        c->state = ST_IDLE;
+        csr_no_matrix(c);
         return rc;
     }
     if (fresh) {
@@ -550,22 +563,50 @@ static int dia_upload(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const d
         s.dia_cap = need;
     }
     s.dia_data = dst;
-    const bool same_kind = c->dia && c->dia_sym == sym;  // a plan chosen on the other kind names another kernel's
-    c->csr_nnz = ndiag * c->n;
-    c->csr_f32 = false;
-    c->bsr_bs = 0;
-    c->bsr_nnzb = 0;
-    c->dia = true;
-    c->dia_sym = sym;
     c->dia_ndiag = ndiag;
     c->dia_ld = pitch;
-    TRY(pc_drop(c));  // the diagonal belonged to the old matrix
-    const auto plan = sym ? plan_spmv_dia_sym : plan_spmv_dia;
-    if (c->csr_plan_user && same_kind)  // the caller's rows per lane, diagonals in flight and policy
-        s.plan = plan(s.dev, s.nloc, ndiag, s.plan.R / 64, s.plan.U, s.plan.nt, 0);
-    else
-        s.plan = plan(s.dev, s.nloc, ndiag, 0, 0, -1, 0), c->csr_plan_user = false;
-    c->state = ST_IDLE;
+    return csr_set_storage(c, sym ? SK_DIA_SYM : SK_DIA, ndiag * c->n, /*f32=*/false);
+}
+
+// cgx_set_dia (sym = false) and cgx_set_dia_sym: the same checks in the same order, then the upload.  The room is
+// counted in stored diagonals, not in the expansion's.
+static int dia_set(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld, bool sym,
+                   const char *what) {
+    if (!c) return fail(CGX_ERR_ARG, "%s: ctx is NULL", what);
+    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "%s: not a cgx_create_csr context", what);
+    if (c->nr)
+        return fail(CGX_ERR_ARG, "%s: not with several right-hand sides (a cgx_create_csr_nrhs context): batched DIA "
+                                 "is not built", what);
+    if (c->csr_multi)
+        return fail(CGX_ERR_ARG, "%s: not over row blocks (a cgx_create_csr_multi context): DIA over row blocks is "
+                                 "not built", what);
+    if (ndiag < 0) return fail(CGX_ERR_ARG, "%s: ndiag must be >= 0 (got %lld)", what, (long long)ndiag);
+    if (ndiag > 0 && (!offsets || !data)) return fail(CGX_ERR_ARG, "%s: offsets / data is NULL", what);
+    if (ld < c->n) return fail(CGX_ERR_SHAPE, "%s: ld = %lld is below n = %lld", what, (long long)ld, (long long)c->n);
+    if (ndiag > c->csr_cap / c->n)  // ndiag n > the room, without the product's overflow
+        return fail(CGX_ERR_SHAPE, "%s: %lld %s of %lld rows are %.0f entries, the context has room for %lld", what,
+                    (long long)ndiag, kDiaKinds[sym].noun, (long long)c->n, (double)ndiag * (double)c->n,
+                    (long long)c->csr_cap);
+    TRY(kDiaKinds[sym].check(c->n, ndiag, offsets));  // nothing is uploaded when it fails
+    return dia_upload(c, ndiag, offsets, data, ld, sym);
+}
+
+// cgx_spmv_dia / cgx_spmv_dia_sym
+static int spmv_dia_any(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld, const void *v,
+                        void *out, void *stream, bool sym, const char *what) {
+    if (n < 0 || ndiag < 0) return fail(CGX_ERR_SHAPE, "%s: bad shape", what);
+    if (ld < n) return fail(CGX_ERR_SHAPE, "%s: ld = %lld is below n = %lld", what, (long long)ld, (long long)n);
+    if ((ndiag > 0 && (!offsets || !data)) || !v || !out) return fail(CGX_ERR_ARG, "%s: NULL pointer", what);
+    const DiaKind &dk = kDiaKinds[sym];
+    int dev = 0;
+    HIPT(hipGetDevice(&dev));
+    RedWs ws;
+    TRY(dev_ws(&ws));
+    HIPT(preload_kernels(dk.preload_spmv));
+    const MatvecPlan pl = dk.plan(dev, n, ndiag, 0, 0, -1, 0);  // the default rule unless the kind's env names a plan
+    HIPT(dk.spmv(pl, static_cast<const int32_t *>(offsets), static_cast<const double *>(data), ld, n, ndiag,
+                 static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
+                 static_cast<hipStream_t>(stream), nullptr, nullptr));
     return CGX_OK;
 }
 
@@ -670,18 +711,23 @@ int cgx_set_precond_block(cgx_ctx *c, int bs) {
     char *dD = nullptr;
     TRY(pc_alloc(s, (int64_t)cnt, &dD));
     auto extract = [&]() -> int {
-        if (c->dia && c->dia_sym)  // the same blocks from the upper diagonals and their mirrors (cgx_dia_sym.hip)
-            HIPT(dia_sym_diag_blocks_f64(c->n, bs, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
-                                         f64(s.dia_data), c->dia_ld, f64(dD), s.stream));
-        else if (c->dia)  // the same blocks from the diagonals (cgx_dia.hip)
-            HIPT(dia_diag_blocks_f64(c->n, bs, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
-                                     f64(s.dia_data), c->dia_ld, f64(dD), s.stream));
-        else if (c->bsr_bs)  // the same blocks from the BSR arrays, for any bs (cgx_bsmv.hip)
-            HIPT(bsr_diag_blocks_f64(c->n, c->bsr_bs, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
-                                     reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(dD), s.stream));
-        else
-            HIPT(csr_diag_blocks_f64(c->n, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
-                                     reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(dD), s.stream));
+        switch (c->storage) {  // the same blocks from every storage
+            case SK_DIA:
+            case SK_DIA_SYM:  // from the diagonals (cgx_dia.hip), or the upper diagonals and their mirrors (cgx_dia_sym.hip)
+                HIPT(dia_kind(c).diag_blocks(c->n, bs, c->dia_ndiag, reinterpret_cast<const int32_t *>(s.csr_ci),
+                                             f64(s.dia_data), c->dia_ld, f64(dD), s.stream));
+                break;
+            case SK_BSR:  // from the BSR arrays, for any bs (cgx_bsmv.hip)
+                HIPT(bsr_diag_blocks_f64(c->n, c->bsr_bs, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                         reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.csr_val), f64(dD),
+                                         s.stream));
+                break;
+            case SK_CSR:
+                HIPT(csr_diag_blocks_f64(c->n, bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                         reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c), f64(dD),
+                                         s.stream));
+                break;
+        }
         HIPT(hipMemcpyAsync(D.data(), dD, cnt * 8, hipMemcpyDeviceToHost, s.stream));
         HIPT(hipStreamSynchronize(s.stream));
         return CGX_OK;
@@ -880,80 +926,22 @@ int cgx_set_bsr(cgx_ctx *c, int bs, const int64_t *brow_ptr, const int32_t *bcol
 
 int cgx_set_dia(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld) {
     const Range range_("cgx_set_dia");
-    if (!c) return fail(CGX_ERR_ARG, "cgx_set_dia: ctx is NULL");
-    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_dia: not a cgx_create_csr context");
-    if (c->nr)
-        return fail(CGX_ERR_ARG, "cgx_set_dia: not with several right-hand sides (a cgx_create_csr_nrhs context): "
-                                 "batched DIA is not built");
-    if (c->csr_multi)
-        return fail(CGX_ERR_ARG, "cgx_set_dia: not over row blocks (a cgx_create_csr_multi context): DIA over row "
-                                 "blocks is not built");
-    if (ndiag < 0) return fail(CGX_ERR_ARG, "cgx_set_dia: ndiag must be >= 0 (got %lld)", (long long)ndiag);
-    if (ndiag > 0 && (!offsets || !data)) return fail(CGX_ERR_ARG, "cgx_set_dia: offsets / data is NULL");
-    if (ld < c->n)
-        return fail(CGX_ERR_SHAPE, "cgx_set_dia: ld = %lld is below n = %lld", (long long)ld, (long long)c->n);
-    if (ndiag > c->csr_cap / c->n)  // ndiag n > the room, without the product's overflow
-        return fail(CGX_ERR_SHAPE, "cgx_set_dia: %lld diagonals of %lld rows are %.0f entries, the context has room for "
-                                   "%lld", (long long)ndiag, (long long)c->n, (double)ndiag * (double)c->n,
-                    (long long)c->csr_cap);
-    TRY(cgx_dia_check(c->n, ndiag, offsets));  // nothing is uploaded when it fails
-    return dia_upload(c, ndiag, offsets, data, ld, /*sym=*/false);
+    return dia_set(c, ndiag, offsets, data, ld, /*sym=*/false, "cgx_set_dia");
 }
 
 int cgx_set_dia_sym(cgx_ctx *c, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld) {
     const Range range_("cgx_set_dia_sym");
-    if (!c) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: ctx is NULL");
-    if (c->op != OP_CSR) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: not a cgx_create_csr context");
-    if (c->nr)
-        return fail(CGX_ERR_ARG, "cgx_set_dia_sym: not with several right-hand sides (a cgx_create_csr_nrhs context): "
-                                 "batched DIA is not built");
-    if (c->csr_multi)
-        return fail(CGX_ERR_ARG, "cgx_set_dia_sym: not over row blocks (a cgx_create_csr_multi context): DIA over row "
-                                 "blocks is not built");
-    if (ndiag < 0) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: ndiag must be >= 0 (got %lld)", (long long)ndiag);
-    if (ndiag > 0 && (!offsets || !data)) return fail(CGX_ERR_ARG, "cgx_set_dia_sym: offsets / data is NULL");
-    if (ld < c->n)
-        return fail(CGX_ERR_SHAPE, "cgx_set_dia_sym: ld = %lld is below n = %lld", (long long)ld, (long long)c->n);
-    if (ndiag > c->csr_cap / c->n)  // the stored count, not the expansion's; without the product's overflow
-        return fail(CGX_ERR_SHAPE, "cgx_set_dia_sym: %lld stored diagonals of %lld rows are %.0f entries, the context has "
-                                   "room for %lld", (long long)ndiag, (long long)c->n, (double)ndiag * (double)c->n,
-                    (long long)c->csr_cap);
-    TRY(cgx_dia_sym_check(c->n, ndiag, offsets));  // nothing is uploaded when it fails
-    return dia_upload(c, ndiag, offsets, data, ld, /*sym=*/true);
+    return dia_set(c, ndiag, offsets, data, ld, /*sym=*/true, "cgx_set_dia_sym");
 }
 
 int cgx_spmv_dia(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld, const void *v,
                  void *out, void *stream) {
-    if (n < 0 || ndiag < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia: bad shape");
-    if (ld < n) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia: ld = %lld is below n = %lld", (long long)ld, (long long)n);
-    if ((ndiag > 0 && (!offsets || !data)) || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_dia: NULL pointer");
-    int dev = 0;
-    HIPT(hipGetDevice(&dev));
-    RedWs ws;
-    TRY(dev_ws(&ws));
-    HIPT(preload_kernels(PL_DIA));
-    const MatvecPlan pl = plan_spmv_dia(dev, n, ndiag);  // the default rule unless CGX_DIA_PLAN names a plan
-    HIPT(spmv_dia_f64(pl, static_cast<const int32_t *>(offsets), static_cast<const double *>(data), ld, n, ndiag,
-                      static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
-                      static_cast<hipStream_t>(stream)));
-    return CGX_OK;
+    return spmv_dia_any(n, ndiag, offsets, data, ld, v, out, stream, /*sym=*/false, "cgx_spmv_dia");
 }
 
 int cgx_spmv_dia_sym(int64_t n, int64_t ndiag, const void *offsets, const void *data, int64_t ld, const void *v,
                      void *out, void *stream) {
-    if (n < 0 || ndiag < 0) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia_sym: bad shape");
-    if (ld < n) return fail(CGX_ERR_SHAPE, "cgx_spmv_dia_sym: ld = %lld is below n = %lld", (long long)ld, (long long)n);
-    if ((ndiag > 0 && (!offsets || !data)) || !v || !out) return fail(CGX_ERR_ARG, "cgx_spmv_dia_sym: NULL pointer");
-    int dev = 0;
-    HIPT(hipGetDevice(&dev));
-    RedWs ws;
-    TRY(dev_ws(&ws));
-    HIPT(preload_kernels(PL_DIA_SYM));
-    const MatvecPlan pl = plan_spmv_dia_sym(dev, n, ndiag);  // the default rule unless CGX_DIA_SYM_PLAN names a plan
-    HIPT(spmv_dia_sym_f64(pl, static_cast<const int32_t *>(offsets), static_cast<const double *>(data), ld, n, ndiag,
-                          static_cast<const double *>(v), static_cast<double *>(out), nullptr, nullptr, ws,
-                          static_cast<hipStream_t>(stream)));
-    return CGX_OK;
+    return spmv_dia_any(n, ndiag, offsets, data, ld, v, out, stream, /*sym=*/true, "cgx_spmv_dia_sym");
 }
 
 int cgx_bsr_tile_values(int64_t nnzb, int bs, const void *values, void *values_tiled, void *stream) {

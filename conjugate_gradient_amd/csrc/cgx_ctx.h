@@ -166,6 +166,9 @@ inline int ring(int64_t j) { return (int)(j & 3); }
 enum Mode { M_SINGLE = 0, M_LOCAL = 1, M_RCCL = 2 };
 enum Op { OP_DENSE = 0, OP_POISSON = 1, OP_CSR = 2 };
 enum State { ST_IDLE = 0, ST_BEGUN = 1, ST_CONVERGED = 2 };
+// A cgx_create_csr context's matrix: scalar CSR (double or float values: cgx_ctx::csr_f32), BSR blocks, every
+// diagonal, or the upper diagonals of a symmetric A (one-sided)
+enum Storage { SK_CSR = 0, SK_BSR = 1, SK_DIA = 2, SK_DIA_SYM = 3 };
 
 constexpr int kEvPairs = 256;
 // CGX_PHASES: the kernels of an iteration that stamp their start / end
@@ -190,13 +193,13 @@ struct Shard {
     // cgx_create_csr: A as row_ptr (int64[n + 1]), col_idx (int32[csr_cap]), values (double[csr_cap], or the
     // first half of it as float[csr_cap] while cgx_ctx::csr_f32); no s.A
     char *csr_rp = nullptr, *csr_ci = nullptr, *csr_val = nullptr;
-    // cgx_set_bsr (cgx_ctx::bsr_bs > 0): csr_rp holds brow_ptr (int64[nb + 1]), csr_ci bcol_idx (int32[nnzb]),
+    // cgx_set_bsr (cgx_ctx::storage SK_BSR): csr_rp holds brow_ptr (int64[nb + 1]), csr_ci bcol_idx (int32[nnzb]),
     // csr_val the values in the host layout (what the preconditioners' extraction reads), and bsr_val the same
     // values in k_bsr_mult_f64's tiled layout: bsr_cap doubles, the library's own memory beside the context's
     // capacity, allocated by the first cgx_set_bsr that needs it and kept until the context goes
     char *bsr_val = nullptr;
     int64_t bsr_cap = 0;
-    // cgx_set_dia (cgx_ctx::dia): csr_ci holds the offsets (int32[ndiag]) and dia_data the diagonals at the pitch
+    // cgx_set_dia / cgx_set_dia_sym (SK_DIA, SK_DIA_SYM): csr_ci holds the offsets (int32[ndiag]) and dia_data the diagonals at the pitch
     // cgx_ctx::dia_ld -- csr_val where ndiag * dia_ld doubles fit the context's capacity, otherwise dia_val, dia_cap
     // doubles of the library's own memory, allocated by the first cgx_set_dia that needs it (an odd n pads the pitch)
     char *dia_val = nullptr, *dia_data = nullptr;
@@ -314,14 +317,14 @@ struct cgx_ctx {
     int64_t csr_cap = 0, csr_nnz = -1;
     bool csr_plan_user = false;
     bool csr_f32 = false;
-    // cgx_set_bsr: the block size while the context is block-valued (0: scalar CSR; the next cgx_set_csr /
-    // cgx_set_csr_f32 goes back to 0), and its stored blocks; csr_nnz is then bsr_nnzb * bsr_bs^2
+    // which storage the matrix is in: the last successful cgx_set_csr / cgx_set_csr_f32 (SK_CSR), cgx_set_bsr,
+    // cgx_set_dia or cgx_set_dia_sym decides it (csr_set_storage, cgx_csr.hip); every dispatch switches on it
+    Storage storage = SK_CSR;
+    // SK_BSR: the block size and the stored blocks; csr_nnz is then bsr_nnzb * bsr_bs^2
     int bsr_bs = 0;
     int64_t bsr_nnzb = 0;
-    // cgx_set_dia: the context is diagonal-valued (until the next cgx_set_csr / cgx_set_csr_f32 / cgx_set_bsr), its
-    // diagonals and their device pitch (n rounded up to even); csr_nnz is then dia_ndiag * n
-    // cgx_set_dia_sym: dia with dia_sym, the stored diagonals those of the upper triangle (one-sided)
-    bool dia = false, dia_sym = false;
+    // SK_DIA, SK_DIA_SYM: the (stored) diagonals and their device pitch (n rounded up to even); csr_nnz is then
+    // dia_ndiag * n
     int64_t dia_ndiag = 0, dia_ld = 0;
     // cgx_create_csr_multi (whatever the block count): csr_cap is every block's room; halo_counts[d * S + q] =
     // the length of block d's list into block q (cgx_get_csr_halo); csr_halo: several blocks exchange p and x
@@ -439,6 +442,28 @@ inline bool a32(const cgx_ctx *c) { return (c->flags & CGX_A_F32) != 0; }
 inline CsrValues csr_values(const cgx_ctx *c) { return CsrValues(c->sh[0].csr_val, c->csr_f32); }
 // ... and row block s's (cgx_create_csr_multi; the one block of any other CSR context)
 inline CsrValues csr_values(const cgx_ctx *c, const Shard &s) { return CsrValues(s.csr_val, c->csr_f32); }
+inline bool is_dia(const cgx_ctx *c) { return c->storage == SK_DIA || c->storage == SK_DIA_SYM; }
+// What differs between the two diagonal kinds on the host side, indexed by sym (SK_DIA_SYM): every place that
+// serves both goes through dia_kind(c), or kDiaKinds[sym] before a context is of the kind.
+struct DiaKind {
+    bool (*plan_ok)(int R, int U, int nt);
+    MatvecPlan (*plan)(int device, int64_t n, int64_t ndiag, int R, int U, int nt, int blocks_per_cu);
+    hipError_t (*spmv)(const MatvecPlan &pl, const int32_t *offsets, const double *data, int64_t ld, int64_t n,
+                       int64_t ndiag, const double *v, double *out, const double *pown, double *dot_out,
+                       const RedWs &ws, hipStream_t s, const int64_t *gate, int64_t *ts);
+    hipError_t (*diag_blocks)(int64_t n, int pbs, int64_t ndiag, const int32_t *offsets, const double *data,
+                              int64_t ld, double *D, hipStream_t s);
+    // the code objects a context loads (CGX_PC_JACOBI's extraction is the diagonal file's), the kernel-level call's
+    unsigned preload_ctx, preload_spmv;
+    int (*check)(int64_t n, int64_t ndiag, const int32_t *offsets);
+    const char *prefix, *noun;  // of the messages
+};
+inline const DiaKind kDiaKinds[2] = {
+    {spmv_dia_plan_ok, plan_spmv_dia, spmv_dia_f64, dia_diag_blocks_f64, PL_DIA, PL_DIA, cgx_dia_check, "",
+     "diagonals"},
+    {spmv_dia_sym_plan_ok, plan_spmv_dia_sym, spmv_dia_sym_f64, dia_sym_diag_blocks_f64, PL_DIA | PL_DIA_SYM,
+     PL_DIA_SYM, cgx_dia_sym_check, "one-sided ", "stored diagonals"}};
+inline const DiaKind &dia_kind(const cgx_ctx *c) { return kDiaKinds[c->storage == SK_DIA_SYM]; }
 inline void *slot(const Shard &s, int i) { return s.scal + 8 * i; }
 inline bool p2p(const cgx_ctx *c) { return (c->flags & CGX_COMM_P2P) != 0; }
 // Where a kernel writes its (partial) scalar: the global slot directly when

@@ -10,27 +10,19 @@
 // streams 8 bytes in place of CSR's 12, a row 8 ndiag + 16 in place of
 // 12 L + 24.
 //
-// One row per lane (R = 1) or two (R = 2, rows (i, i + 1) with i even): a wave
-// owns 64 R consecutive rows, waves walk these groups with a grid stride as
-// for_row_groups does (cgx_matvec_core.h).  With R = 2 a diagonal of even offset
-// loads data and v with 16-byte loads (i + o is even; the host side sees to an
-// even pitch and 16-byte aligned bases, and passes vec = 0 where a kernel-level
-// caller's arrays are not: then every load is 8 bytes, the bits the same); an
-// odd offset takes 8-byte loads.  The loads of U diagonals (data, then v) are
-// issued before their FMAs.  data is read once (load_a: default policy or
-// non-temporal), v is the only reused data (default policy).
+// The kernel is cgx_dia_core.h's walk (rows per lane, groups, the fused p.Ap)
+// over the terms below.  With R = 2 a diagonal of even offset loads data and v
+// with 16-byte loads (i + o is even), an odd offset takes 8-byte loads.  data is
+// read once (load_a: default policy or non-temporal), v is the only reused data
+// (default policy).
 //
-// Range test without a branch around a load.  The offsets are wave-uniform
-// (scalar loads); every wave reads them once for their minimum and maximum.  A
-// group of rows is interior when every diagonal reaches every one of its rows,
-//     g0 + min(0, min o) >= 0  and  g0 + 64 R - 1 + max(0, max o) < n,
-// and then runs with no test at all.  The other groups (the first and last
-// max |o| rows, a partial last group) run one row at a time: the column is
-// clamped into the diagonal's own range [max(0, o), min(n, n + o)), loaded, and
-// the term selected away before the FMA.  So nothing is read outside v[0 .. n)
-// or outside the slots of a diagonal that hold an entry of A, and a NaN in an
-// unused slot never reaches an accumulator.  Which path a row takes does not
-// change its bits.
+// Range rule.  A group of rows is interior when every diagonal reaches every
+// one of its rows,
+//     g0 + min(0, min o) >= 0  and  g0 + 64 R - 1 + max(0, max o) < n.
+// In the other groups (the first and last max |o| rows, a partial last group)
+// the column is clamped into the diagonal's own range [max(0, o), min(n, n + o)).
+// So nothing is read outside v[0 .. n) or outside the slots of a diagonal that
+// hold an entry of A, and a NaN in an unused slot never reaches an accumulator.
 //
 // Summation order (a contract, include/cgx.h "Diagonal storage";
 // tests/_dia_order.py states it on the CPU).  Row i starts from +0.0 and, for
@@ -40,91 +32,71 @@
 // terms, a stored zero is a term.  A row's sum depends on nothing but the
 // matrix and v: not on R, U, the load policy, the grid or the pitch.  A row no
 // diagonal reaches gives +0.0.
-//
-// The fused p.Ap goes through store_row / grid_sum_last_block_n<1> as in the CSR
-// kernel: deterministic for a given (R, grid).
-//
-// No atomics, no spin-waits in k_dia_mult_f64: plain vector loads and stores
-// (the reduction hand-off is cgx_device.h's).
 #include <algorithm>
 
-#include "cgx_matvec_core.h"
+#include "cgx_dia_core.h"
 
 namespace cgx {
 namespace {
 
-// U diagonals from k0 on, every row of the lane in range: loads, then FMAs in stored order.
-template <int R, int U, int NT>
-__device__ __forceinline__ void dia_interior(const int32_t *__restrict__ offsets, const double *__restrict__ data,
-                                             int64_t ld, const double *__restrict__ v, int64_t i0, int64_t k0,
-                                             bool vec, double (&acc)[R]) {
-    double a[U][R], x[U][R];
+// Every diagonal as stored: one term per diagonal and row.
+struct FullTerms {
+    // U diagonals from k0 on, every row of the lane in range: loads (data, then v), then FMAs in stored order.
+    template <int R, int U, int NT>
+    static __device__ __forceinline__ void interior(const int32_t *__restrict__ offsets,
+                                                    const double *__restrict__ data, int64_t ld,
+                                                    const double *__restrict__ v, int64_t i0, int64_t k0, bool vec,
+                                                    double (&acc)[R]) {
+        double a[U][R], x[U][R];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t o = offsets[k0 + u];
-        const double *ap = data + (k0 + u) * ld + o + i0;
-        if constexpr (R == 2) {
-            if (vec && !(o & 1)) {
-                const d2 t = load_a<NT>(reinterpret_cast<const d2 *>(ap));
-                a[u][0] = t.x;
-                a[u][1] = t.y;
-            } else {
-                a[u][0] = load_a<NT>(ap);
-                a[u][1] = load_a<NT>(ap + 1);
-            }
-        } else {
-            a[u][0] = load_a<NT>(ap);
+        for (int u = 0; u < U; ++u) {
+            const int64_t o = offsets[k0 + u];
+            load_piece<R, NT>(data + (k0 + u) * ld + o + i0, vec && !(o & 1), a[u]);
         }
-    }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t o = offsets[k0 + u];
-        const double *vp = v + o + i0;
-        if constexpr (R == 2) {
-            if (vec && !(o & 1)) {
-                const d2 t = *reinterpret_cast<const d2 *>(vp);
-                x[u][0] = t.x;
-                x[u][1] = t.y;
-            } else {
-                x[u][0] = vp[0];
-                x[u][1] = vp[1];
-            }
-        } else {
-            x[u][0] = vp[0];
+        for (int u = 0; u < U; ++u) {
+            const int64_t o = offsets[k0 + u];
+            load_piece<R, 0>(v + o + i0, vec && !(o & 1), x[u]);
         }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] = __builtin_fma(a[u][r], x[u][r], acc[r]);
     }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = __builtin_fma(a[u][r], x[u][r], acc[r]);
-}
 
-// U diagonals from k0 on for one row that some diagonal may miss (or that is
-// past the end): the column clamped into the diagonal's range, 8-byte loads,
-// the term selected away.
-template <int U, int NT>
-__device__ __forceinline__ void dia_guarded(const int32_t *__restrict__ offsets, const double *__restrict__ data,
-                                            int64_t ld, const double *__restrict__ v, int64_t n, int64_t i,
-                                            int64_t k0, double &acc) {
-    double a[U], x[U];
-    bool ok[U];
+    // U diagonals from k0 on for one row that some diagonal may miss (or that is
+    // past the end): the column clamped into the diagonal's range, 8-byte loads,
+    // the term selected away.
+    template <int U, int NT>
+    static __device__ __forceinline__ void guarded(const int32_t *__restrict__ offsets,
+                                                   const double *__restrict__ data, int64_t ld,
+                                                   const double *__restrict__ v, int64_t n, int64_t i, int64_t k0,
+                                                   double &acc) {
+        double a[U], x[U];
+        bool ok[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t o = offsets[k0 + u];
-        const int64_t j = i + o;
-        const int64_t lo = o > 0 ? o : 0, hi = (o < 0 ? n + o : n) - 1;  // the diagonal's columns, lo <= hi as |o| < n
-        ok[u] = i < n && j >= lo && j <= hi;
-        int64_t jc = j < lo ? lo : j > hi ? hi : j;
-        jc = jc < 0 ? 0 : jc >= n ? n - 1 : jc;  // an unchecked offset of the kernel-level call stays inside the arrays
-        a[u] = load_a<NT>(data + (k0 + u) * ld + jc);
-        x[u] = v[jc];
-    }
+        for (int u = 0; u < U; ++u) {
+            const int64_t o = offsets[k0 + u];
+            const int64_t j = i + o;
+            const int64_t lo = o > 0 ? o : 0, hi = (o < 0 ? n + o : n) - 1;  // the diagonal's columns, lo <= hi as |o| < n
+            ok[u] = i < n && j >= lo && j <= hi;
+            int64_t jc = j < lo ? lo : j > hi ? hi : j;
+            jc = jc < 0 ? 0 : jc >= n ? n - 1 : jc;  // an unchecked offset of the kernel-level call stays inside the arrays
+            a[u] = load_a<NT>(data + (k0 + u) * ld + jc);
+            x[u] = v[jc];
+        }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const double t = __builtin_fma(a[u], x[u], acc);
-        acc = ok[u] ? t : acc;
+        for (int u = 0; u < U; ++u) {
+            const double t = __builtin_fma(a[u], x[u], acc);
+            acc = ok[u] ? t : acc;
+        }
     }
-}
+
+    // every diagonal reaches every row of the group
+    static __device__ __forceinline__ bool is_interior(int64_t g0, int RW, int64_t omin, int64_t omax, int64_t n) {
+        return g0 + omin >= 0 && g0 + RW - 1 + omax < n;
+    }
+};
 
 template <int R, int U, int NT>
 __global__ __launch_bounds__(kNT) void k_dia_mult_f64(const int32_t *__restrict__ offsets,
@@ -133,64 +105,14 @@ __global__ __launch_bounds__(kNT) void k_dia_mult_f64(const int32_t *__restrict_
                                                        double *__restrict__ out, const double *__restrict__ pown,
                                                        double *dot_out, double *partials, unsigned *ticket,
                                                        const int64_t *gate, int64_t *ts) {
-    if (gate && *gate) return;  // the solve stopped in an earlier iteration (device-side gating)
-    ts_start(ts);
-    constexpr int RW = 64 * R;  // rows per wave
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int64_t ngroups = (n + RW - 1) / RW;
-    const int64_t wstride = (int64_t)gridDim.x * (kNT / 64);
-    int64_t omin = 0, omax = 0;  // min(0, min offset), max(0, max offset): wave-uniform
-    for (int64_t k = 0; k < ndiag; ++k) {
-        const int64_t o = offsets[k];
-        omin = o < omin ? o : omin;
-        omax = o > omax ? o : omax;
-    }
-    const int64_t kfull = ndiag - ndiag % U;
-    double dacc[1] = {0.0};
-    for (int64_t g = (int64_t)blockIdx.x * (kNT / 64) + wid; g < ngroups; g += wstride) {
-        const int64_t g0 = g * RW, i0 = g0 + (int64_t)lane * R;
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.0;
-        if (g0 + omin >= 0 && g0 + RW - 1 + omax < n) {  // interior: every diagonal reaches every row of the group
-            for (int64_t k0 = 0; k0 < kfull; k0 += U) dia_interior<R, U, NT>(offsets, data, ld, v, i0, k0, vec != 0, acc);
-            for (int64_t k0 = kfull; k0 < ndiag; ++k0) dia_interior<R, 1, NT>(offsets, data, ld, v, i0, k0, vec != 0, acc);
-        } else {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                for (int64_t k0 = 0; k0 < kfull; k0 += U) dia_guarded<U, NT>(offsets, data, ld, v, n, i0 + r, k0, acc[r]);
-                for (int64_t k0 = kfull; k0 < ndiag; ++k0) dia_guarded<1, NT>(offsets, data, ld, v, n, i0 + r, k0, acc[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            if (i0 + r < n) store_row(i0 + r, acc[r], out, pown, dacc[0]);
-    }
-    if (pown) grid_sum_last_block_n<1>(dacc, partials, ticket, dot_out, 1u);
-    ts_end(ts);
+    dia_walk<FullTerms, R, U, NT>(offsets, data, ld, n, ndiag, vec, v, out, pown, dot_out, partials, ticket, gate, ts);
 }
 
-using DiaFn = decltype(&k_dia_mult_f64<1, 1, 0>);  // the same type at every (R, U, policy)
-
-template <int R, int NT>
-DiaFn pick_dia_u(int U) {
-    switch (U) {
-        case 1: return k_dia_mult_f64<R, 1, NT>;
-        case 2: return k_dia_mult_f64<R, 2, NT>;
-        case 4: return k_dia_mult_f64<R, 4, NT>;
-        case 8: return k_dia_mult_f64<R, 8, NT>;
-        default: return nullptr;
-    }
-}
-template <int NT>
-DiaFn pick_dia_nt(int R, int U) {
-    return R == 1 ? pick_dia_u<1, NT>(U) : R == 2 ? pick_dia_u<2, NT>(U) : nullptr;
-}
-// The instantiated plan's kernel, or nullptr: R rows per lane (1 or 2), U diagonals in flight, load policy 2 or 8.
-DiaFn pick_dia(int R, int U, int nt) {
-    return nt == 8 ? pick_dia_nt<1>(R, U) : nt == 2 ? pick_dia_nt<0>(R, U) : nullptr;
-}
+struct FullKernels {
+    template <int R, int U, int NT>
+    static DiaFn fn() { return k_dia_mult_f64<R, U, NT>; }
+};
+using Host = DiaHost<FullKernels>;
 
 // One-time set-up, one row per lane: what k_csr_diag_minv (cgx_pcg.hip) gives
 // on the expanded matrix bit for bit.  The expansion lists row i's entries
@@ -246,13 +168,10 @@ __global__ __launch_bounds__(kNT) void k_dia_diag_blocks(int64_t n, int pbs, int
 
 }  // namespace
 
-bool spmv_dia_plan_ok(int R, int U, int nt) { return pick_dia(R, U, nt) != nullptr; }
+bool spmv_dia_plan_ok(int R, int U, int nt) { return Host::plan_ok(R, U, nt); }
 
-// R / U <= 0, nt < 0, blocks_per_cu <= 0 pick the defaults.
+// R / U <= 0, nt < 0, blocks_per_cu <= 0 pick the defaults (the rule is DiaHost::plan's, under CGX_DIA_PLAN).
 MatvecPlan plan_spmv_dia(int device, int64_t n, int64_t ndiag, int R, int U, int nt, int blocks_per_cu) {
-    MatvecPlan pl;
-    pl.csr = 1;
-    pl.dia = 1;
     // Measured on MI355X, every (R, U, policy) interleaved in five rounds in one
     // process with k_csr_mult_f64's plans on the same matrix (tools/dia_ab.py,
     // profiles/dia_ab_*.jsonl; ms per launch, round-to-round spread below 0.9 %
@@ -277,34 +196,13 @@ MatvecPlan plan_spmv_dia(int device, int64_t n, int64_t ndiag, int R, int U, int
     // at 65): nothing but v is read twice.  Diagonal counts other than 5 and 65 and
     // matrices below 0.5 GB are not measured.
     (void)ndiag;
-    const int r0 = 1, u0 = 1, n0 = 8;
-    int r = r0, u = u0;
-    pl.nt = n0;
-    // CGX_DIA_PLAN = "R=..,U=..,nt=..,bpc=..": taken when it names an instantiated plan, then the arguments
-    const char *env = "CGX_DIA_PLAN";
-    const int eR = env_opt(env, "R", r), eU = env_opt(env, "U", u), en = env_opt(env, "nt", pl.nt);
-    if (spmv_dia_plan_ok(eR, eU, en)) r = eR, u = eU, pl.nt = en;
-    if (R > 0) r = R;
-    if (U > 0) u = U;
-    if (nt >= 0) pl.nt = nt;
-    if (!spmv_dia_plan_ok(r, u, pl.nt)) r = r0, u = u0, pl.nt = n0;
-    pl.R = 64 * r;
-    pl.U = u;
-    pl.blocks = plan_grid(reinterpret_cast<const void *>(pick_dia(r, u, pl.nt)), device, n, pl.R, 8, env, blocks_per_cu);
-    return pl;
+    return Host::plan(device, n, R, U, nt, blocks_per_cu, /*r0=*/1, /*u0=*/1, /*n0=*/8, "CGX_DIA_PLAN", /*pl.dia=*/1);
 }
 
 hipError_t spmv_dia_f64(const MatvecPlan &pl, const int32_t *offsets, const double *data, int64_t ld, int64_t n,
                         int64_t ndiag, const double *v, double *out, const double *pown, double *dot_out,
                         const RedWs &ws, hipStream_t s, const int64_t *gate, int64_t *ts) {
-    if (n <= 0) return hipSuccess;
-    if (!pl.dia || pl.R % 64 || !spmv_dia_plan_ok(pl.R / 64, pl.U, pl.nt) || pl.blocks < 1 ||
-        pl.blocks > kMaxRedBlocks || ndiag < 0 || ld < n)
-        return hipErrorInvalidValue;
-    const int vec = (ld % 2 == 0 && al16(data) && al16(v)) ? 1 : 0;  // the 16-byte loads of R = 2
-    hipLaunchKernelGGL(pick_dia(pl.R / 64, pl.U, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, offsets, data, ld, n, ndiag,
-                       vec, v, out, pown, dot_out, ws.partials, ws.tickets + T_MATVEC, gate, ts);
-    return hipGetLastError();
+    return Host::launch(pl, 1, offsets, data, ld, n, ndiag, v, out, pown, dot_out, ws, s, gate, ts);
 }
 
 hipError_t dia_diag_minv_f64(int64_t n, int64_t ndiag, const int32_t *offsets, const double *data, int64_t ld,
@@ -324,10 +222,6 @@ hipError_t dia_diag_blocks_f64(int64_t n, int pbs, int64_t ndiag, const int32_t 
     return hipGetLastError();
 }
 
-// Load this file's code object on the current device now (see preload_kernels).
-hipError_t preload_dia() {
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_dia_mult_f64<1, 1, 0>));
-}
+hipError_t preload_dia() { return Host::preload(); }
 
 }  // namespace cgx

@@ -1,7 +1,8 @@
 // cgx_dia_sym.hip -- the one-sided diagonal matVec of a symmetric A held by the
 // diagonals of its upper triangle (cgx_set_dia_sym): k_dia_sym_mult_f64, its
 // plan rule and the one-time extraction of the block preconditioner's blocks, a
-// code object of its own (k_dia_mult_f64's ISA does not move).
+// code object of its own.  The kernel is cgx_dia_core.h's walk (rows per lane,
+// groups, the 16-byte loads, the fused p.Ap) over the terms below.
 //
 // Storage: scipy's dia_matrix of triu(A).  offsets int32[ndiag], 0 <= o < n,
 // data double[ndiag * ld], data[k * ld + j] = A[j - o][j] for j in [o, n).  The
@@ -14,135 +15,113 @@
 // memory when the second use still finds its line on the die.  The upper piece
 // (the first use in the walk's order) is a default-policy load, the lower piece
 // (the last use; all of an offset-0 diagonal) takes the plan's policy, 2 or 8.
+// With R = 2 the lower data piece is always one 16-byte load (even pitch,
+// aligned base, i even); the upper data piece and both v pieces are when o is
+// even.
 //
-// The shape is k_dia_mult_f64's (cgx_dia.hip): one row per lane (R = 1) or two
-// (R = 2, rows (i, i + 1), i even), a wave owns 64 R consecutive rows, waves walk
-// the groups with a grid stride.  With R = 2 the lower data piece is always one
-// 16-byte load (even pitch, aligned base, i even); the upper data piece and both
-// v pieces are when o is even; vec = 0 (an odd pitch or unaligned arrays of a
-// kernel-level caller) makes every load 8 bytes, the bits the same.  The loads
-// of U stored diagonals are issued before their FMAs.
-//
-// Range test without a branch around a load.  The offsets are wave-uniform
-// (scalar loads); every wave reads them once for their maximum.  A group of
-// rows is interior when both terms of every stored diagonal reach every one of
-// its rows, g0 - omax >= 0 and g0 + 64 R - 1 + omax < n, and then runs with no
-// test at all.  The other groups run one row at a time: the slot is clamped
-// into the diagonal's own range [o, n), the vector index into [0, n), loaded,
-// and the term selected away before the FMA.  Nothing is read outside v[0 .. n)
-// or outside a diagonal's slots [o, n), and a NaN in an unused slot never
-// reaches an accumulator.  An unchecked offset of the kernel-level call (o < 0
-// or o >= n) adds no term and reads nothing outside the arrays: a negative one
-// sends every group down the clamped path.
+// Range rule.  A group of rows is interior when both terms of every stored
+// diagonal reach every one of its rows, g0 - omax >= 0 and
+// g0 + 64 R - 1 + omax < n.  In the other groups the slot is clamped into the
+// diagonal's own range [o, n) and the vector index into [0, n).  Nothing is read
+// outside v[0 .. n) or outside a diagonal's slots [o, n), and a NaN in an unused
+// slot never reaches an accumulator.  An unchecked offset of the kernel-level
+// call (o < 0 or o >= n) adds no term and reads nothing outside the arrays: a
+// negative one sends every group down the clamped path.
 //
 // Summation order (a contract, include/cgx.h "One-sided diagonal storage";
 // tests/_dia_sym.py states it on the CPU).  Row i starts from +0.0 and, for
 // k = 0 .. ndiag-1 in stored order, does the upper term, then the lower term,
 // each acc = fma(a, x, acc) where it exists: one accumulator per row, no
 // cross-lane combine.  That is, bit for bit, k_dia_mult_f64 on the expansion
-// (every stored o > 0 as the two consecutive diagonals o, -o).  A row's sum
-// depends on nothing but the matrix and v: not on R, U, the load policy, the
-// grid or the pitch.
-//
-// The fused p.Ap goes through store_row / grid_sum_last_block_n<1> as in
-// k_dia_mult_f64: the same bits as that kernel on the expansion at the same R
-// and grid.
-//
-// No atomics, no spin-waits in k_dia_sym_mult_f64: plain vector loads and
-// stores (the reduction hand-off is cgx_device.h's).
+// (every stored o > 0 as the two consecutive diagonals o, -o), the fused p.Ap
+// included at the same R and grid.  A row's sum depends on nothing but the
+// matrix and v: not on R, U, the load policy, the grid or the pitch.
 #include <algorithm>
 
-#include "cgx_matvec_core.h"
+#include "cgx_dia_core.h"
 
 namespace cgx {
 namespace {
 
-// R consecutive doubles from p: one 16-byte load when wide (R = 2), 8-byte loads otherwise.
-template <int R, int NT>
-__device__ __forceinline__ void load_piece(const double *__restrict__ p, bool wide, double (&d)[R]) {
-    if constexpr (R == 2) {
-        if (wide) {
-            const d2 t = load_a<NT>(reinterpret_cast<const d2 *>(p));
-            d[0] = t.x;
-            d[1] = t.y;
-        } else {
-            d[0] = load_a<NT>(p);
-            d[1] = load_a<NT>(p + 1);
+// A stored diagonal and its mirror: up to two terms per stored diagonal and row.
+struct SymTerms {
+    // U stored diagonals from k0 on, both terms of each in range for every row of the
+    // lane (0 <= o <= i0, i0 + R - 1 + o < n): loads, then FMAs in the contract's order.
+    template <int R, int U, int NT>
+    static __device__ __forceinline__ void interior(const int32_t *__restrict__ offsets,
+                                                    const double *__restrict__ data, int64_t ld,
+                                                    const double *__restrict__ v, int64_t i0, int64_t k0, bool vec,
+                                                    double (&acc)[R]) {
+        double au[U][R], xu[U][R], al[U][R], xl[U][R];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t o = offsets[k0 + u];
+            const double *row = data + (k0 + u) * ld + i0;
+            const bool even = vec && !(o & 1);
+            if (o > 0) load_piece<R, 0>(row + o, even, au[u]);  // first use: the line stays on the die
+            load_piece<R, NT>(row, vec, al[u]);                 // last use
         }
-    } else {
-        d[0] = load_a<NT>(p);
-    }
-}
-
-// U stored diagonals from k0 on, both terms of each in range for every row of the
-// lane (0 <= o <= i0, i0 + R - 1 + o < n): loads, then FMAs in the contract's order.
-template <int R, int U, int NT>
-__device__ __forceinline__ void sym_interior(const int32_t *__restrict__ offsets, const double *__restrict__ data,
-                                             int64_t ld, const double *__restrict__ v, int64_t i0, int64_t k0,
-                                             bool vec, double (&acc)[R]) {
-    double au[U][R], xu[U][R], al[U][R], xl[U][R];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t o = offsets[k0 + u];
-        const double *row = data + (k0 + u) * ld + i0;
-        const bool even = vec && !(o & 1);
-        if (o > 0) load_piece<R, 0>(row + o, even, au[u]);  // first use: the line stays on the die
-        load_piece<R, NT>(row, vec, al[u]);                 // last use
-    }
+        for (int u = 0; u < U; ++u) {
+            const int64_t o = offsets[k0 + u];
+            const bool even = vec && !(o & 1);
+            if (o > 0) load_piece<R, 0>(v + i0 + o, even, xu[u]);
+            load_piece<R, 0>(v + i0 - o, even, xl[u]);
+        }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t o = offsets[k0 + u];
-        const bool even = vec && !(o & 1);
-        if (o > 0) load_piece<R, 0>(v + i0 + o, even, xu[u]);
-        load_piece<R, 0>(v + i0 - o, even, xl[u]);
-    }
+        for (int u = 0; u < U; ++u) {
+            const bool up = offsets[k0 + u] > 0;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const bool up = offsets[k0 + u] > 0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (up) acc[r] = __builtin_fma(au[u][r], xu[u][r], acc[r]);
-            acc[r] = __builtin_fma(al[u][r], xl[u][r], acc[r]);
+            for (int r = 0; r < R; ++r) {
+                if (up) acc[r] = __builtin_fma(au[u][r], xu[u][r], acc[r]);
+                acc[r] = __builtin_fma(al[u][r], xl[u][r], acc[r]);
+            }
         }
     }
-}
 
-// U stored diagonals from k0 on for one row that a term may miss (or that is past
-// the end): slots clamped into [o, n), vector indices into [0, n), 8-byte loads,
-// the terms selected away.
-template <int U, int NT>
-__device__ __forceinline__ void sym_guarded(const int32_t *__restrict__ offsets, const double *__restrict__ data,
-                                            int64_t ld, const double *__restrict__ v, int64_t n, int64_t i, int64_t k0,
-                                            double &acc) {
-    double au[U], xu[U], al[U], xl[U];
-    bool oku[U], okl[U];
+    // U stored diagonals from k0 on for one row that a term may miss (or that is past
+    // the end): slots clamped into [o, n), vector indices into [0, n), 8-byte loads,
+    // the terms selected away.
+    template <int U, int NT>
+    static __device__ __forceinline__ void guarded(const int32_t *__restrict__ offsets,
+                                                   const double *__restrict__ data, int64_t ld,
+                                                   const double *__restrict__ v, int64_t n, int64_t i, int64_t k0,
+                                                   double &acc) {
+        double au[U], xu[U], al[U], xl[U];
+        bool oku[U], okl[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t o = offsets[k0 + u];
-        const bool valid = o >= 0 && o < n && i < n;  // an unchecked offset of the kernel-level call adds no term
-        oku[u] = valid && o > 0 && i + o < n;
-        okl[u] = valid && i - o >= 0;
-        const int64_t lo = o < 0 ? 0 : o > n - 1 ? n - 1 : o;  // the first slot of the diagonal, inside the array
-        int64_t ju = i + o;  // the upper term's slot and vector index
-        ju = ju < lo ? lo : ju > n - 1 ? n - 1 : ju;
-        int64_t jl = i;  // the lower term's slot ...
-        jl = jl < lo ? lo : jl > n - 1 ? n - 1 : jl;
-        int64_t jv = jl - o;  // ... and its vector index
-        jv = jv < 0 ? 0 : jv > n - 1 ? n - 1 : jv;
-        const double *row = data + (k0 + u) * ld;
-        au[u] = load_a<0>(row + ju);
-        xu[u] = v[ju];
-        al[u] = load_a<NT>(row + jl);
-        xl[u] = v[jv];
-    }
+        for (int u = 0; u < U; ++u) {
+            const int64_t o = offsets[k0 + u];
+            const bool valid = o >= 0 && o < n && i < n;  // an unchecked offset of the kernel-level call adds no term
+            oku[u] = valid && o > 0 && i + o < n;
+            okl[u] = valid && i - o >= 0;
+            const int64_t lo = o < 0 ? 0 : o > n - 1 ? n - 1 : o;  // the first slot of the diagonal, inside the array
+            int64_t ju = i + o;  // the upper term's slot and vector index
+            ju = ju < lo ? lo : ju > n - 1 ? n - 1 : ju;
+            int64_t jl = i;  // the lower term's slot ...
+            jl = jl < lo ? lo : jl > n - 1 ? n - 1 : jl;
+            int64_t jv = jl - o;  // ... and its vector index
+            jv = jv < 0 ? 0 : jv > n - 1 ? n - 1 : jv;
+            const double *row = data + (k0 + u) * ld;
+            au[u] = load_a<0>(row + ju);
+            xu[u] = v[ju];
+            al[u] = load_a<NT>(row + jl);
+            xl[u] = v[jv];
+        }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const double t = __builtin_fma(au[u], xu[u], acc);
-        acc = oku[u] ? t : acc;
-        const double w = __builtin_fma(al[u], xl[u], acc);
-        acc = okl[u] ? w : acc;
+        for (int u = 0; u < U; ++u) {
+            const double t = __builtin_fma(au[u], xu[u], acc);
+            acc = oku[u] ? t : acc;
+            const double w = __builtin_fma(al[u], xl[u], acc);
+            acc = okl[u] ? w : acc;
+        }
     }
-}
+
+    // both terms of every diagonal reach every row (omin < 0: an unchecked offset)
+    static __device__ __forceinline__ bool is_interior(int64_t g0, int RW, int64_t omin, int64_t omax, int64_t n) {
+        return omin >= 0 && g0 - omax >= 0 && g0 + RW - 1 + omax < n;
+    }
+};
 
 template <int R, int U, int NT>
 __global__ __launch_bounds__(kNT) void k_dia_sym_mult_f64(const int32_t *__restrict__ offsets,
@@ -151,64 +130,14 @@ __global__ __launch_bounds__(kNT) void k_dia_sym_mult_f64(const int32_t *__restr
                                                            double *__restrict__ out, const double *__restrict__ pown,
                                                            double *dot_out, double *partials, unsigned *ticket,
                                                            const int64_t *gate, int64_t *ts) {
-    if (gate && *gate) return;  // the solve stopped in an earlier iteration (device-side gating)
-    ts_start(ts);
-    constexpr int RW = 64 * R;  // rows per wave
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int64_t ngroups = (n + RW - 1) / RW;
-    const int64_t wstride = (int64_t)gridDim.x * (kNT / 64);
-    int64_t omin = 0, omax = 0;  // min(0, min offset) (< 0: an unchecked offset), max(0, max offset): wave-uniform
-    for (int64_t k = 0; k < ndiag; ++k) {
-        const int64_t o = offsets[k];
-        omin = o < omin ? o : omin;
-        omax = o > omax ? o : omax;
-    }
-    const int64_t kfull = ndiag - ndiag % U;
-    double dacc[1] = {0.0};
-    for (int64_t g = (int64_t)blockIdx.x * (kNT / 64) + wid; g < ngroups; g += wstride) {
-        const int64_t g0 = g * RW, i0 = g0 + (int64_t)lane * R;
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.0;
-        if (omin >= 0 && g0 - omax >= 0 && g0 + RW - 1 + omax < n) {  // interior: both terms of every diagonal, every row
-            for (int64_t k0 = 0; k0 < kfull; k0 += U) sym_interior<R, U, NT>(offsets, data, ld, v, i0, k0, vec != 0, acc);
-            for (int64_t k0 = kfull; k0 < ndiag; ++k0) sym_interior<R, 1, NT>(offsets, data, ld, v, i0, k0, vec != 0, acc);
-        } else {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                for (int64_t k0 = 0; k0 < kfull; k0 += U) sym_guarded<U, NT>(offsets, data, ld, v, n, i0 + r, k0, acc[r]);
-                for (int64_t k0 = kfull; k0 < ndiag; ++k0) sym_guarded<1, NT>(offsets, data, ld, v, n, i0 + r, k0, acc[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            if (i0 + r < n) store_row(i0 + r, acc[r], out, pown, dacc[0]);
-    }
-    if (pown) grid_sum_last_block_n<1>(dacc, partials, ticket, dot_out, 1u);
-    ts_end(ts);
+    dia_walk<SymTerms, R, U, NT>(offsets, data, ld, n, ndiag, vec, v, out, pown, dot_out, partials, ticket, gate, ts);
 }
 
-using DiaSymFn = decltype(&k_dia_sym_mult_f64<1, 1, 0>);  // the same type at every (R, U, policy)
-
-template <int R, int NT>
-DiaSymFn pick_sym_u(int U) {
-    switch (U) {
-        case 1: return k_dia_sym_mult_f64<R, 1, NT>;
-        case 2: return k_dia_sym_mult_f64<R, 2, NT>;
-        case 4: return k_dia_sym_mult_f64<R, 4, NT>;
-        case 8: return k_dia_sym_mult_f64<R, 8, NT>;
-        default: return nullptr;
-    }
-}
-template <int NT>
-DiaSymFn pick_sym_nt(int R, int U) {
-    return R == 1 ? pick_sym_u<1, NT>(U) : R == 2 ? pick_sym_u<2, NT>(U) : nullptr;
-}
-// The instantiated plan's kernel, or nullptr: R rows per lane (1 or 2), U stored diagonals in flight, policy 2 or 8.
-DiaSymFn pick_sym(int R, int U, int nt) {
-    return nt == 8 ? pick_sym_nt<1>(R, U) : nt == 2 ? pick_sym_nt<0>(R, U) : nullptr;
-}
+struct SymKernels {
+    template <int R, int U, int NT>
+    static DiaFn fn() { return k_dia_sym_mult_f64<R, U, NT>; }
+};
+using Host = DiaHost<SymKernels>;
 
 // One-time set-up, one row per lane over the nblk * pbs rows of the diagonal
 // blocks: what k_csr_diag_blocks (cgx_pcg_block.hip) gives on the expansion bit
@@ -251,13 +180,10 @@ __global__ __launch_bounds__(kNT) void k_dia_sym_diag_blocks(int64_t n, int pbs,
 
 }  // namespace
 
-bool spmv_dia_sym_plan_ok(int R, int U, int nt) { return pick_sym(R, U, nt) != nullptr; }
+bool spmv_dia_sym_plan_ok(int R, int U, int nt) { return Host::plan_ok(R, U, nt); }
 
-// R / U <= 0, nt < 0, blocks_per_cu <= 0 pick the defaults.
+// R / U <= 0, nt < 0, blocks_per_cu <= 0 pick the defaults (the rule is DiaHost::plan's, under CGX_DIA_SYM_PLAN).
 MatvecPlan plan_spmv_dia_sym(int device, int64_t n, int64_t ndiag, int R, int U, int nt, int blocks_per_cu) {
-    MatvecPlan pl;
-    pl.csr = 1;
-    pl.dia = 2;
     // Measured on MI355X, every (R, U, policy) interleaved in five rounds in one
     // process with k_dia_mult_f64's plans on the full matrix (tools/dia_sym_ab.py,
     // profiles/dia_sym_ab_*.jsonl; ms per launch, round-to-round spread 2.0 % on
@@ -280,34 +206,13 @@ MatvecPlan plan_spmv_dia_sym(int device, int64_t n, int64_t ndiag, int R, int U,
     // default at every size.  The non-temporal policy on the last use loses 5-8 %
     // at R = 2.  Stored counts other than 3 and 33 are not measured.
     (void)ndiag;
-    const int r0 = 2, u0 = 8, n0 = 2;
-    int r = r0, u = u0;
-    pl.nt = n0;
-    // CGX_DIA_SYM_PLAN = "R=..,U=..,nt=..,bpc=..": taken when it names an instantiated plan, then the arguments
-    const char *env = "CGX_DIA_SYM_PLAN";
-    const int eR = env_opt(env, "R", r), eU = env_opt(env, "U", u), en = env_opt(env, "nt", pl.nt);
-    if (spmv_dia_sym_plan_ok(eR, eU, en)) r = eR, u = eU, pl.nt = en;
-    if (R > 0) r = R;
-    if (U > 0) u = U;
-    if (nt >= 0) pl.nt = nt;
-    if (!spmv_dia_sym_plan_ok(r, u, pl.nt)) r = r0, u = u0, pl.nt = n0;
-    pl.R = 64 * r;
-    pl.U = u;
-    pl.blocks = plan_grid(reinterpret_cast<const void *>(pick_sym(r, u, pl.nt)), device, n, pl.R, 8, env, blocks_per_cu);
-    return pl;
+    return Host::plan(device, n, R, U, nt, blocks_per_cu, /*r0=*/2, /*u0=*/8, /*n0=*/2, "CGX_DIA_SYM_PLAN", /*pl.dia=*/2);
 }
 
 hipError_t spmv_dia_sym_f64(const MatvecPlan &pl, const int32_t *offsets, const double *data, int64_t ld, int64_t n,
                             int64_t ndiag, const double *v, double *out, const double *pown, double *dot_out,
                             const RedWs &ws, hipStream_t s, const int64_t *gate, int64_t *ts) {
-    if (n <= 0) return hipSuccess;
-    if (pl.dia != 2 || pl.R % 64 || !spmv_dia_sym_plan_ok(pl.R / 64, pl.U, pl.nt) || pl.blocks < 1 ||
-        pl.blocks > kMaxRedBlocks || ndiag < 0 || ld < n)
-        return hipErrorInvalidValue;
-    const int vec = (ld % 2 == 0 && al16(data) && al16(v)) ? 1 : 0;  // the 16-byte loads of R = 2
-    hipLaunchKernelGGL(pick_sym(pl.R / 64, pl.U, pl.nt), dim3(pl.blocks), dim3(kNT), 0, s, offsets, data, ld, n, ndiag,
-                       vec, v, out, pown, dot_out, ws.partials, ws.tickets + T_MATVEC, gate, ts);
-    return hipGetLastError();
+    return Host::launch(pl, 2, offsets, data, ld, n, ndiag, v, out, pown, dot_out, ws, s, gate, ts);
 }
 
 hipError_t dia_sym_diag_blocks_f64(int64_t n, int pbs, int64_t ndiag, const int32_t *offsets, const double *data,
@@ -319,10 +224,6 @@ hipError_t dia_sym_diag_blocks_f64(int64_t n, int pbs, int64_t ndiag, const int3
     return hipGetLastError();
 }
 
-// Load this file's code object on the current device now (see preload_kernels).
-hipError_t preload_dia_sym() {
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_dia_sym_mult_f64<1, 1, 0>));
-}
+hipError_t preload_dia_sym() { return Host::preload(); }
 
 }  // namespace cgx

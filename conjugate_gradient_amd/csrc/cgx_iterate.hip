@@ -108,24 +108,28 @@ int matvec_sym_streamed(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, in
 int launch_matvec(cgx_ctx *c, Shard &s, const char *vec, bool with_dot, int dot_slot, bool gated) {
     TRY(timing_begin(c, s));
     const bool streamed = (c->flags & CGX_HOST_STREAM) != 0;
-    if (c->op == OP_CSR && c->dia && c->dia_sym)  // one-sided (cgx_set_dia_sym): the same place, the one-sided kernel
-        HIPT(spmv_dia_sym_f64(s.plan, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data), c->dia_ld, s.nloc,
-                              c->dia_ndiag, f64(vec), f64(s.Ap), with_dot ? f64(s.pown) : nullptr,
-                              with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream, gate_of(s, gated)));
-    else if (c->op == OP_CSR && c->dia)  // diagonal-valued (cgx_set_dia): the same place in the iteration, the diagonal kernel
-        HIPT(spmv_dia_f64(s.plan, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data), c->dia_ld, s.nloc,
-                          c->dia_ndiag, f64(vec), f64(s.Ap), with_dot ? f64(s.pown) : nullptr,
-                          with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream, gate_of(s, gated)));
-    else if (c->op == OP_CSR && c->bsr_bs)  // block-valued (cgx_set_bsr): the same place in the iteration, the block kernel
-        HIPT(spmv_bsr_f64(s.plan, c->bsr_bs, reinterpret_cast<const int64_t *>(s.csr_rp),
-                          reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.bsr_val), s.nloc / c->bsr_bs, f64(vec),
-                          f64(s.Ap), with_dot ? f64(s.pown) : nullptr, with_dot ? slot_f64(s, dot_slot) : nullptr,
-                          s.ws, s.stream, gate_of(s, gated)));
-    else if (c->op == OP_CSR)  // the indices were checked on the host before they were uploaded (cgx_set_csr)
-        HIPT(spmv_csr_f64(s.plan, reinterpret_cast<const int64_t *>(s.csr_rp),
-                          reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c, s), s.nloc, f64(vec), f64(s.Ap),
-                          with_dot ? f64(s.pown) : nullptr, with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws, s.stream,
-                          gate_of(s, gated)));
+    if (c->op == OP_CSR) {  // the same place in the iteration for every storage of the matrix
+        const double *pown = with_dot ? f64(s.pown) : nullptr;
+        double *dot = with_dot ? slot_f64(s, dot_slot) : nullptr;
+        switch (c->storage) {
+            case SK_DIA:
+            case SK_DIA_SYM:  // the kind's diagonal kernel
+                HIPT(dia_kind(c).spmv(s.plan, reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.dia_data), c->dia_ld,
+                                      s.nloc, c->dia_ndiag, f64(vec), f64(s.Ap), pown, dot, s.ws, s.stream,
+                                      gate_of(s, gated), nullptr));
+                break;
+            case SK_BSR:  // the block kernel
+                HIPT(spmv_bsr_f64(s.plan, c->bsr_bs, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                  reinterpret_cast<const int32_t *>(s.csr_ci), f64(s.bsr_val), s.nloc / c->bsr_bs,
+                                  f64(vec), f64(s.Ap), pown, dot, s.ws, s.stream, gate_of(s, gated)));
+                break;
+            case SK_CSR:  // the indices were checked on the host before they were uploaded (cgx_set_csr)
+                HIPT(spmv_csr_f64(s.plan, reinterpret_cast<const int64_t *>(s.csr_rp),
+                                  reinterpret_cast<const int32_t *>(s.csr_ci), csr_values(c, s), s.nloc, f64(vec),
+                                  f64(s.Ap), pown, dot, s.ws, s.stream, gate_of(s, gated)));
+                break;
+        }
+    }
     else if (c->op == OP_POISSON)
         HIPT(stencil5_f64(f64(vec), s.nloc / c->m, c->m, f64(s.Ap), with_dot ? slot_f64(s, dot_slot) : nullptr, s.ws,
                           s.stream, gate_of(s, gated)));

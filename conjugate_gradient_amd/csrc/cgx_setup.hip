@@ -864,13 +864,17 @@ int cgx_get_info(const cgx_ctx *c, cgx_info *info) {
                   ((c->mode == M_LOCAL && c->xchg_kernels) ? CGX_PULL_ACTIVE : 0) |
                   ((c->fuse_combine || c->fuse_f32) ? CGX_FOLDED_ACTIVE : 0) | (c->halo_pull ? CGX_HALO_PULL_ACTIVE : 0) |
                   (c->pool ? CGX_THREADS_ACTIVE : 0) | (c->halo_overlap ? CGX_HALO_OVERLAP_ACTIVE : 0);
-    if (c->op == OP_CSR)
+    if (c->op == OP_CSR) {
         info->flags |= CGX_CSR_ACTIVE | (c->pc_kind != CGX_PC_NONE ? CGX_PRECOND_ACTIVE : 0) |
                        (c->csr_f32 ? CGX_A_F32 : 0) |  // float-valued since cgx_set_csr_f32
-                       (c->bsr_bs ? CGX_BSR_ACTIVE : 0) |  // block-valued since cgx_set_bsr
-                       (c->dia ? CGX_DIA_ACTIVE : 0) |  // diagonal-valued since cgx_set_dia / cgx_set_dia_sym
-                       (c->dia && c->dia_sym ? CGX_DIA_SYM_ACTIVE : 0) |  // ... by the upper diagonals alone
                        (c->csr_halo ? CGX_CSR_HALO_ACTIVE : 0);
+        switch (c->storage) {
+            case SK_CSR: break;
+            case SK_BSR: info->flags |= CGX_BSR_ACTIVE; break;  // block-valued since cgx_set_bsr
+            case SK_DIA: info->flags |= CGX_DIA_ACTIVE; break;  // diagonal-valued since cgx_set_dia
+            case SK_DIA_SYM: info->flags |= CGX_DIA_ACTIVE | CGX_DIA_SYM_ACTIVE; break;  // ... by the upper diagonals alone
+        }
+    }
     info->elem_bytes = c->es;
     return CGX_OK;
 }

@@ -8,7 +8,7 @@ full diagonals o, -o), on which k_dia_mult_f64 and a CSR context are already tes
   3. contexts: a from_dia_sym solver against a from_dia solver on the expansion, bit for bit -- fixed loops from a rough
      x0, every host form of a converged solve, every preconditioner kind, the preconditioner set-up against a CSR
      context, residual_norm, the fused p.Ap;
-  4. the lifecycle and the refusals; 5. `cg_hip --csr --dia-sym`."""
+  4. the lifecycle, one context through every storage kind, and the refusals; 5. `cg_hip --csr --dia-sym`."""
 import functools
 
 import numpy as np
@@ -427,6 +427,75 @@ def test_lifecycle_and_failed_calls():
         assert f & cg.CGX_DIA_ACTIVE and not f & DIA_SYM_ACTIVE and s.matvec_plan() == plan_d
         got = solve0(s, n)
         assert same_bits(got[0], want_d[0]) and got[1:] == want_d[1:]
+    no_hip_error()
+
+
+def transition_matrix(n=38):
+    """A symmetric, diagonally dominant matrix of small integers that fits a context with room for 5 n entries in
+    every storage: one-sided offsets (0, 1, 37), so the expansion (0, 1, -1, 37, -37) is 5 diagonals; the couplings
+    (i, i + 1) between two 2 x 2 blocks are zero except at i = 1 mod 4, so bs = 2 stores 39 blocks (156 entries).
+    With p of signed powers of two every product and every partial sum of A p, p.p and p.Ap is an integer below
+    2^53: the bits depend on no summation order, and one statement serves the CSR, BSR and diagonal kernels."""
+    i = np.arange(n)
+    data = np.zeros((3, n))
+    data[0] = 16.0
+    data[1, 1:] = np.where((i[:-1] % 2 == 0) | (i[:-1] % 4 == 1), (i[:-1] % 3) - 3.0, 0.0)  # A[i][i + 1] at slot i + 1
+    data[2, 37:] = 2.0
+    offsets = np.array([0, 1, 37], np.int32)
+    eo, ed = ds.expand(offsets, ds.mask_unused(offsets, data, n), n)
+    A = do.dense(eo, np.nan_to_num(ed), n)
+    assert np.array_equal(A, A.T) and np.count_nonzero(A) <= 5 * n
+    rows, cols = np.nonzero(A)
+    csr = (np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int64), cols.astype(np.int32),
+           A[rows, cols])
+    bsr = bo.from_dense(A, 2)
+    assert bsr[2].size <= 5 * n
+    p = np.where(i % 3 == 0, -1.0, 1.0) * 2.0 ** (i % 4)
+    return offsets, ds.mask_unused(offsets, data, n), eo, ed, csr, bsr, p
+
+
+def test_storage_transitions_on_one_context(monkeypatch):
+    """One context through every storage kind: after each upload the plan, the storage flags and the matVec.  A plan
+    the caller chose carries over exactly between CSR and BSR (T and the policy; the grid follows the rows) and is
+    dropped by every step that enters or leaves a diagonal kind or switches between the two.  The expected plans are
+    the plan rules' on this matrix (CSR: mean row length 2, T = 2; a diagonal kind's defaults; n = 38 is one group
+    of a diagonal kernel and one block), the same on the commit before the kinds shared one upload tail.
+    The context hands out neither A p nor p.Ap, so: A p through residual_norm with x = p and b = the CPU statement's
+    A p on the expansion (||b - A x|| is 0.0 exactly when every row has its value; this launch has no fused dot), and
+    the fused p.Ap through one iteration from x0 = 0 with b = p, where x_1 = fl(p.p / p.Ap) p bit for bit."""
+    for env in ("CGX_SPMV_PLAN", "CGX_BSMV_PLAN", "CGX_DIA_PLAN", "CGX_DIA_SYM_PLAN", "CGX_GATED"):
+        monkeypatch.delenv(env, raising=False)
+    n = 38
+    offsets, data, eo, ed, csr, bsr, p = transition_matrix(n)
+    Ap = do.spmv_dia(eo, ed, p)
+    assert same_bits(Ap, do.dense(eo, np.nan_to_num(ed), n) @ p) and float(p @ Ap) > 0.0  # exact in any order
+    x1 = (float(p @ p) / float(p @ Ap)) * p
+    BSR, DIA, SYM = cg.CGX_BSR_ACTIVE, cg.CGX_DIA_ACTIVE, DIA_SYM_ACTIVE
+    plan = lambda R, U, nt, blocks: dict(R=R, U=U, nt=nt, blocks=blocks)  # noqa: E731
+    steps = (
+        ("set_csr", lambda s: s.set_csr(*csr), plan(32, 1, 2, 1), 0),
+        ("set_matvec_plan (CSR)", lambda s: s.set_matvec_plan(8, 1, 8), plan(8, 1, 8, 2), 0),
+        ("set_bsr", lambda s: s.set_bsr(*bsr), plan(8, 1, 8, 1), BSR),  # T = 8 and policy 8 kept, 19 block rows
+        ("set_dia", lambda s: s.set_dia(eo, ed), plan(64, 1, 8, 1), DIA),  # dropped: the full kind's default
+        ("set_matvec_plan (DIA)", lambda s: s.set_matvec_plan(128, 4, 2), plan(128, 4, 2, 1), DIA),
+        ("set_dia_sym", lambda s: s.set_dia_sym(offsets, data), plan(128, 8, 2, 1), DIA | SYM),  # dropped
+        ("set_dia", lambda s: s.set_dia(eo, ed), plan(64, 1, 8, 1), DIA),
+        ("set_csr_f32", lambda s: s.set_csr(*csr, a_f32=True), plan(32, 1, 2, 1), 0),
+        ("set_csr", lambda s: s.set_csr(*csr), plan(32, 1, 2, 1), 0),
+    )
+    with cg.Solver(n, csr_nnz=5 * n) as s:
+        for k, (name, step, want_plan, want_flags) in enumerate(steps):
+            step(s)
+            assert s.matvec_plan() == want_plan, (k, name, s.matvec_plan())
+            assert s.info.flags & (BSR | DIA | SYM) == want_flags, (k, name, hex(s.info.flags))
+            assert bool(s.info.flags & cg.CGX_A_F32) == (name == "set_csr_f32"), (k, name)
+            s.set_rows(0, b_rows=Ap, x_rows=p)
+            assert s.residual_norm() == (0.0, float(np.sqrt(Ap @ Ap))), (k, name, s.residual_norm())
+            s.set_rows(0, b_rows=p, x_rows=np.zeros(n))
+            s.begin()
+            assert s.iterate(1) == (1, False)
+            got = s.get_x()
+            assert same_bits(got, x1), (k, name, np.flatnonzero(got != x1))
     no_hip_error()
 
 
